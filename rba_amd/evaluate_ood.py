@@ -128,7 +128,9 @@ def build_parser():
 class GraphedScore:
     """score_func(model, x[None]) replayed from one captured hipGraph per image shape, for ONE stream.  The first call of a shape
     runs eagerly (lazy per-shape state of the model), the second captures, later calls copy the image into the static input and
-    replay.  The returned map is a fresh tensor (the static output is overwritten by the next replay)."""
+    replay.  The returned map is a fresh tensor (the static output is overwritten by the next replay).
+    The key is the image shape ONLY: a captured graph keeps replaying the weights it was captured with.  After a weight change, drop this object and
+    make a new one (MaskFormer's own graphs are keyed on the weights and need nothing)."""
 
     MAX_SHAPES = 4
 

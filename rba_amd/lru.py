@@ -7,7 +7,14 @@ cache, the entries of a captured shape look idle and would be the first to be ev
 feet).  Every entry that is looked up while the current stream is being captured is therefore PINNED: it is never evicted and does
 not count against ``maxsize`` (the number of live graphs is bounded by their owners).  An entry that would have to be BUILT during
 a capture is returned without being inserted: its tensors live in that graph's private pool and hold garbage until the first
-replay, so no other caller may ever see them."""
+replay, so no other caller may ever see them.
+
+The rule is wider than this class: EVERY tensor a capture reads must stay alive, unchanged, for as long as the graph can be replayed.
+Per-shape constants and per-batch-size constants of the weights (the decoder's initial prediction heads) live in ShapeCaches for that
+reason; the weight images keyed on (data_ptr, _version) of their sources (split planes, token planes, K7 block images, bias fragments,
+folded BatchNorm) are replaced only after a source changed, and a source change changes MaskFormer's graph key, so no graph of the
+model replays them afterwards.  A graph captured OUTSIDE the model (bench.py, evaluate_ood.GraphedScore) keys on the image shape
+only: its owner must drop it after a weight change."""
 from collections import OrderedDict
 
 import torch
@@ -42,6 +49,9 @@ class ShapeCache:
         else:
             d.move_to_end(key)
         return v
+
+    def __contains__(self, key):
+        return key in self._pinned or key in self._d
 
     def pinned(self):
         return len(self._pinned)

@@ -5,6 +5,8 @@ device, identical to the reference, so the unmodified ``get_RbA`` / ``get_logits
 In addition each result dict carries ``"rba"`` ([H,W], the RbA score of evaluate_ood.py:150 produced by the same
 fused kernel) and, on request, ``"argmax"``; ``model.rba_scores(...)`` skips materialising ``sem_seg`` altogether.
 """
+import itertools
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -16,6 +18,21 @@ from .modeling.backbone import resnet as _resnet  # noqa: F401  (registers build
 from .modeling.backbone import swin as _swin  # noqa: F401  (registers D2SwinTransformer)
 from .modeling.meta_arch import mask_former_head as _head  # noqa: F401
 from .registry import BACKBONE_REGISTRY, META_ARCH_REGISTRY, SEM_SEG_HEADS_REGISTRY
+
+# Generation of the module trees of this process: torch's global registration hooks fire whenever any module gets a parameter, buffer or submodule set
+# (construction, load_state_dict(assign=True), `mod.weight = nn.Parameter(..)`, a submodule swap); MaskFormer._weights_version walks its tree again only
+# after that.  A hook that returns None changes nothing.
+_REGISTRATIONS = [0]
+_EPOCHS = itertools.count(1)
+
+
+def _registered(*_):
+    _REGISTRATIONS[0] += 1
+
+
+for _hook in (nn.modules.module.register_module_parameter_registration_hook, nn.modules.module.register_module_buffer_registration_hook,
+              nn.modules.module.register_module_module_registration_hook):
+    _hook(_registered)
 
 
 def _class_prob(mask_cls):
@@ -239,15 +256,27 @@ class MaskFormer(nn.Module):
         return out
 
     def _weights_version(self):
-        # the Parameter OBJECTS of a module tree are stable (load_state_dict copies in place, .to() swaps .data): walk the tree once, then sum the versions of a
-        # flat list -- the generator walk cost 0.3 ms per call, which a serial caller pays in front of every image's first launch (round 6)
-        flat = self.__dict__.get("_param_flat")
-        if flat is None:
-            flat = self.__dict__["_param_flat"] = list(self.parameters())
+        """The weights' part of the graph key: (epoch, sum of the versions) over a flat list of every parameter AND buffer (BatchNorm statistics are read
+        by the graphs too).  The module tree is walked only when torch's global module-registration hooks fired since the last call (a parameter, buffer
+        or submodule was set anywhere: load_state_dict(assign=True), `mod.weight = nn.Parameter(..)`, a submodule swap); the walk -- 1.3 ms for Swin-B,
+        paid by a serial caller in front of every image's first launch -- is never per call.  The epoch moves when the walk finds other objects or a
+        tensor's data pointer moved (`p.data = t` changes no version); within an epoch versions only grow, so their sum changes with every in-place edit.
+        Not seen (as by every weight cache of this package): in-place edits through `p.data`, which bypass the version counter."""
+        st = self.__dict__.get("_param_flat")
+        gen = _REGISTRATIONS[0]
+        if st is None or st[0] != gen:
+            flat = list(self.parameters()) + list(self.buffers())
+            same = st is not None and len(flat) == len(st[2]) and all(a is b for a, b in zip(flat, st[2]))
+            st = self.__dict__["_param_flat"] = [gen, st[1] if same else next(_EPOCHS), flat, st[3] if same else None]
         v = 0
-        for p_ in flat:
-            v += p_._version
-        return v
+        for t_ in st[2]:
+            v += t_._version
+        ptrs = [t_.data_ptr() for t_ in st[2]]
+        if ptrs != st[3]:
+            if st[3] is not None:
+                st[1] = next(_EPOCHS)
+            st[3] = ptrs
+        return st[1], v
 
     def _graph_key(self, image, return_argmax, score):
         return (tuple(image.shape), image.dtype, image.device, torch.cuda.current_stream(image.device).cuda_stream, bool(return_argmax), score,

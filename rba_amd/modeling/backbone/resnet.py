@@ -32,8 +32,10 @@ class ConvBN(nn.Module):
         self._folded = None
 
     def folded(self):
+        """(weight * scale, bias - running_mean * scale) with scale = norm.weight / sqrt(running_var + eps): rebuilt when any of the five sources
+        is edited in place or replaced (key: data pointer and version of each)"""
         n = self.norm
-        key = (self.weight.data_ptr(), self.weight._version, n.weight._version, n.running_var._version, self.weight.device)
+        key = (self.weight.device,) + tuple((t.data_ptr(), t._version) for t in (self.weight, n.weight, n.bias, n.running_mean, n.running_var))
         if self._folded is None or self._folded[0] != key:
             scale = n.weight * torch.rsqrt(n.running_var + n.eps)
             w = (self.weight * scale.view(-1, 1, 1, 1)).contiguous(memory_format=torch.channels_last)

@@ -47,11 +47,11 @@ class WindowAttention(nn.Module):
 
     def gathered_bias(self):
         """[nH, N, N] relative-position bias (swin.py:148-155), gathered once per weight load."""
-        t = self.relative_position_bias_table
-        key = (t.data_ptr(), t._version, t.device)
+        t, idx = self.relative_position_bias_table, self.relative_position_index
+        key = (t.data_ptr(), t._version, t.device, idx.data_ptr(), idx._version)
         if self._bias_cache is None or self._bias_cache[0] != key:
             N = self.window_size ** 2
-            b = t[self.relative_position_index.view(-1)].view(N, N, -1).permute(2, 0, 1).contiguous()
+            b = t[idx.view(-1)].view(N, N, -1).permute(2, 0, 1).contiguous()
             frag = ops.swin_bias_fragments(b, self.window_size) if b.is_cuda else None
             self._bias_cache = (key, b, frag)
         return self._bias_cache[1], self._bias_cache[2]
@@ -180,14 +180,18 @@ class PatchEmbed(nn.Module):
         B, Cin, H, W = x.shape
         Wh, Ww = H // ps, W // ps
         cols = x.reshape(B, Cin, Wh, ps, Ww, ps).permute(0, 2, 4, 1, 3, 5).reshape(B, Wh * Ww, Cin * ps * ps).contiguous()     # reshape: channels_last / sliced inputs too, as conv2d took them
-        w = self.proj.weight
-        key = (w.data_ptr(), w._version, w.device)
+        x = ops.linear(cols, self._linear_view())
+        return ops.add_layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)[1], Wh, Ww
+
+    def _linear_view(self):
+        """proj as an nn.Linear over the patch's 3 ps^2 values (weight [C, 3 ps^2] view, bias), cached per weight load"""
+        w, b = self.proj.weight, self.proj.bias
+        key = (w.data_ptr(), w._version, w.device, None if b is None else b.data_ptr())      # the view holds the bias OBJECT: a replaced bias is a new key
         c = getattr(self, "_rba_lin", None)
         if c is None or c[0] != key:
             from types import SimpleNamespace
-            c = self._rba_lin = (key, SimpleNamespace(weight=w.detach().reshape(w.shape[0], -1), bias=self.proj.bias))
-        x = ops.linear(cols, c[1])
-        return ops.add_layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)[1], Wh, Ww
+            c = self._rba_lin = (key, SimpleNamespace(weight=w.detach().reshape(w.shape[0], -1), bias=b))
+        return c[1]
 
     def fused_ok(self):
         w = self.proj.weight

@@ -27,8 +27,8 @@ class _LinearView:
 
 def _cached_linear_view(mod):
     """The nn.Linear view of a 1x1 convolution module, cached on the module per weight load."""
-    w = mod.weight
-    key = (w.data_ptr(), w._version, w.device)
+    w, b = mod.weight, mod.bias
+    key = (w.data_ptr(), w._version, w.device, None if b is None else b.data_ptr())      # the view holds the bias OBJECT: a replaced bias is a new key
     c = getattr(mod, "_rba_lin", None)
     if c is None or c[0] != key:
         c = (key, _LinearView(w.view(w.shape[0], -1), mod.bias))
@@ -194,8 +194,8 @@ class MSDeformAttnPixelDecoder(nn.Module):
 
     @staticmethod
     def _cached(mod, name, build):
-        w = mod.weight
-        key = (w.data_ptr(), w._version, w.device)
+        w, b = mod.weight, getattr(mod, "bias", None)
+        key = (w.data_ptr(), w._version, w.device, None if b is None else b.data_ptr())  # views built here hold the bias OBJECT
         c = getattr(mod, name, None)
         if c is None or c[0] != key:
             c = (key, build())

@@ -35,7 +35,7 @@ class MSDeformAttn(nn.Module):
     def _sampling_linear(self):
         """[sampling_offsets ; attention_weights] stacked along the output dimension, rebuilt when either weight changes."""
         so, aw = self.sampling_offsets, self.attention_weights
-        key = (so.weight.data_ptr(), so.weight._version, aw.weight.data_ptr(), aw.weight._version, so.bias._version, aw.bias._version)
+        key = tuple((t.data_ptr(), t._version) for t in (so.weight, aw.weight, so.bias, aw.bias))
         cache = getattr(self, "_rba_sampling", None)
         if cache is None or cache[0] != key:
             from types import SimpleNamespace

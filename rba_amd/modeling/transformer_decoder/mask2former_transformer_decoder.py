@@ -226,20 +226,26 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
     def _initial_query_side(self, B, device):
         """The prediction heads BEFORE the first layer (reference :427-430) see `query_feat.weight` -- learnt parameters, not the image: decoder_norm, class_embed
         and the three mask_embed Linears of that call are constants of the checkpoint.  Computed once per (weights version, batch size) with the same kernels
-        (bit-identical to evaluating them per image) and kept: five launches and the query tensor's expand + copy less per image (round 6)."""
+        (bit-identical to evaluating them per image) and kept: five launches and the query tensor's expand + copy less per image (round 6).
+        One entry per (batch size, device, weights) in a ShapeCache: a captured graph reads these tensors by address, so an entry looked up during a capture
+        is pinned -- a call with another batch size or other weights adds an entry and never frees one a graph still replays."""
         ps = [self.query_feat.weight, self.decoder_norm.weight, self.decoder_norm.bias, self.class_embed.weight, self.class_embed.bias]
         for ly in self.mask_embed.layers:
             ps += [ly.weight, ly.bias]
         key = (B, device, tuple((p_.data_ptr(), p_._version) for p_ in ps))
-        c = self.__dict__.get("_rba_heads0")
-        if c is None or c[0] != key:
-            if torch.cuda.is_current_stream_capturing():
-                return None                                           # never build a cache entry inside a capture: evaluate in line instead
+        cache = self.__dict__.get("_rba_heads0")
+        if cache is None:
+            cache = self.__dict__["_rba_heads0"] = ShapeCache(4)
+        if key not in cache and torch.cuda.is_current_stream_capturing():
+            return None                                               # never build a cache entry inside a capture: evaluate in line instead
+
+        def build():
             output = self.query_feat.weight[None].expand(B, -1, -1).contiguous()
             side = self._query_side_heads(output)
             torch.cuda.current_stream(device).synchronize()          # once per checkpoint: forwards on OTHER streams read these tensors without an event
-            c = self.__dict__["_rba_heads0"] = (key, output, side)
-        return c[1], c[2]
+            return output, side
+
+        return cache.get(key, build)
 
     def forward_prediction_heads(self, output, mask_features, attn_mask_target_size, need_attn_mask=True, need_masks=True,
                                  gathered=None, query_side=None):

@@ -619,3 +619,207 @@ def test_model_zoo_check_table_checkpoint_formats_and_comparison(tmp_path, capsy
     assert Z.main(["--models_folder", str(models), "--out_path", str(out), "--results-only"]) == 1          # swin_l_1dl has no results.pkl: MISSING rows
     assert "MISSING" in capsys.readouterr().out
     assert Z.main(["--models_folder", str(models), "--out_path", str(out), "--selected_models", "not_in_the_table", "--results-only"]) == 2
+
+
+def _cpu_model(name, seed=0):
+    from rba_amd.checkpoint import load_checkpoint
+    from rba_amd.maskformer_model import MaskFormer
+    a = A.complete(A.ARCHS[name])
+    return load_checkpoint(MaskFormer(a), A.seeded_weights(a, seed)).eval(), a
+
+
+def _replace_param(mod, attr, like=None):
+    """`mod.<attr> = nn.Parameter(new values)`; returns the old Parameter"""
+    old = getattr(mod, attr)
+    new = (old.detach() * 1.25 + 0.01) if like is None else like
+    setattr(mod, attr, torch.nn.Parameter(new.clone()))
+    return old
+
+
+def _set_data(p):
+    p.data = p.detach() * 0.75 - 0.02
+
+
+@torch.no_grad()
+def _in_place(t):
+    t.mul_(1.0)                                   # same values, new version: an in-place edit as load_state_dict / an optimiser step makes it
+
+
+@pytest.mark.parametrize("name", ["tiny1", "r50_1dl"])
+def test_weights_key_follows_every_kind_of_weight_change(name):
+    """The weights' part of MaskFormer's graph key changes under every way of changing a weight -- load_state_dict (copy and assign=True), a submodule swap,
+    a new Parameter set on a module, `p.data = t`, in-place edits of a parameter and of a buffer -- is stable while nothing changes, walks the module tree
+    only after a registration (never per call), and lets go of replaced Parameters."""
+    import gc
+    import weakref
+    from rba_amd.maskformer_model import MaskFormer
+    model, a = _cpu_model(name)
+    sd1 = A.seeded_weights(a, 1)
+    mods = dict(model.named_modules())
+    pred = model.sem_seg_head.predictor
+    conv_bn = model.backbone.stem.conv1 if name == "r50_1dl" else None
+    params = ["sem_seg_head.predictor.query_feat.weight", "sem_seg_head.predictor.decoder_norm.weight",
+              "sem_seg_head.predictor.transformer_cross_attention_layers.0.multihead_attn.in_proj_weight",
+              "sem_seg_head.pixel_decoder.transformer.encoder.layers.0.self_attn.value_proj.weight"]
+    if name == "tiny1":
+        params += ["backbone.layers.0.blocks.0.mlp.fc1.weight", "backbone.layers.0.blocks.0.attn.qkv.weight",
+                   "backbone.layers.0.blocks.0.attn.relative_position_bias_table"]
+    else:
+        params += ["backbone.stem.conv1.weight", "backbone.res2.0.conv1.norm.bias"]
+
+    def owner(path):
+        m_, _, attr = path.rpartition(".")
+        return mods[m_] if m_ else model, attr
+
+    changes = [("load_state_dict copy", lambda: model.load_state_dict(sd1, strict=False)),
+               ("load_state_dict assign", lambda: model.load_state_dict({k: v.clone() for k, v in sd1.items()}, strict=False, assign=True)),
+               ("class_embed swap", lambda: setattr(pred, "class_embed", torch.nn.Linear(pred.class_embed.in_features, pred.class_embed.out_features)))]
+    for path in params:
+        changes.append((f"new Parameter {path}", lambda path=path: _replace_param(*owner(path))))
+        changes.append((f".data = {path}", lambda path=path: _set_data(getattr(*owner(path)))))
+        changes.append((f"in-place {path}", lambda path=path: _in_place(getattr(*owner(path)))))
+    if conv_bn is not None:
+        changes.append(("in-place running_mean", lambda: conv_bn.norm.running_mean.add_(0.5)))
+        changes.append(("in-place running_var", lambda: conv_bn.norm.running_var.mul_(2.0)))
+        changes.append(("new running_mean buffer", lambda: setattr(conv_bn.norm, "running_mean", conv_bn.norm.running_mean + 1.0)))
+    else:
+        idx = mods["backbone.layers.0.blocks.0.attn"].relative_position_index
+        changes.append(("in-place relative_position_index", lambda: idx.add_(0)))
+    changes.append(("in-place pixel_mean buffer", lambda: model.pixel_mean.add_(0.0)))
+    v = model._weights_version()
+    assert model._weights_version() == v
+    for what, change in changes:
+        change()
+        v1 = model._weights_version()
+        assert v1 != v, what
+        assert model._weights_version() == v1, what                     # stable while nothing changes
+        v = v1
+
+    # no module walk per call: after the first call the flat list serves every call until something is registered
+    flat_parameters, flat_buffers = MaskFormer.parameters, MaskFormer.buffers
+
+    def walked(*args, **kwargs):
+        raise AssertionError("_weights_version walked the module tree on a call where nothing was registered")
+    try:
+        MaskFormer.parameters, MaskFormer.buffers = walked, walked
+        for _ in range(3):
+            assert model._weights_version() == v
+    finally:
+        MaskFormer.parameters, MaskFormer.buffers = flat_parameters, flat_buffers
+
+    # replaced Parameters are not kept alive by the key's flat list
+    w_old = weakref.ref(pred.decoder_norm.weight)
+    b_old = weakref.ref(_replace_param(pred.class_embed, "bias"))
+    pred.decoder_norm.weight = torch.nn.Parameter(pred.decoder_norm.weight.detach() + 1.0)
+    assert model._weights_version() != v
+    gc.collect()
+    assert w_old() is None and b_old() is None
+
+
+def _edits(mod, attr, buffer=False, positive=False):
+    """the ways a source tensor changes: in place, `.data =` (parameters), replaced by a new Parameter / buffer tensor"""
+    def val(t):
+        return (t.detach() * 1.5 + 0.25).abs() + 0.5 if positive else t.detach() * 1.5 - 0.25
+
+    @torch.no_grad()
+    def in_place():
+        t = getattr(mod, attr)
+        t.copy_(val(t))
+
+    def set_data():
+        t = getattr(mod, attr)
+        t.data = val(t).clone()
+
+    def replace():
+        t = val(getattr(mod, attr)).clone()
+        setattr(mod, attr, t if buffer else torch.nn.Parameter(t))
+    return [(f"{attr} in place", in_place), (f"{attr} replaced", replace)] + ([] if buffer else [(f"{attr}.data =", set_data)])
+
+
+def test_conv_bn_fold_follows_all_five_sources():
+    """ResNet's ConvBN.folded() (BatchNorm folded into the convolution, cached per weight load) is rebuilt when ANY of weight, norm.weight, norm.bias,
+    norm.running_mean, norm.running_var changes -- in place or by replacement -- and equals a fresh fold and a float64 fold to fp32 rounding."""
+    from rba_amd.modeling.backbone.resnet import ConvBN
+    torch.manual_seed(0)
+    cb = ConvBN(8, 16, 3, padding=1).eval()
+    with torch.no_grad():
+        cb.norm.weight.uniform_(0.5, 1.5); cb.norm.bias.uniform_(-1, 1)
+        cb.norm.running_mean.uniform_(-1, 1); cb.norm.running_var.uniform_(0.5, 2.0)
+    edits = (_edits(cb, "weight") + _edits(cb.norm, "weight") + _edits(cb.norm, "bias")
+             + _edits(cb.norm, "running_mean", buffer=True) + _edits(cb.norm, "running_var", buffer=True, positive=True))
+    for what, edit in [("initial", lambda: None)] + edits:
+        before = [t.clone() for t in cb.folded()]
+        edit()
+        w, b = cb.folded()
+        fresh = ConvBN(8, 16, 3, padding=1).eval()
+        fresh.load_state_dict(cb.state_dict())
+        fw, fb = fresh.folded()
+        assert torch.equal(w, fw) and torch.equal(b, fb), what
+        if what != "initial":
+            assert not (torch.equal(w, before[0]) and torch.equal(b, before[1])), what
+        n = cb.norm
+        scale = n.weight.double() / torch.sqrt(n.running_var.double() + n.eps)
+        w64 = cb.weight.double() * scale.view(-1, 1, 1, 1)
+        b64 = n.bias.double() - n.running_mean.double() * scale
+        eps32 = 2.0 ** -23
+        assert ((w.double() - w64).abs() <= 4 * eps32 * w64.abs() + 1e-30).all(), what
+        assert ((b.double() - b64).abs() <= 4 * eps32 * (n.bias.double().abs() + (n.running_mean.double() * scale).abs())).all(), what
+
+
+def test_weight_derived_views_follow_every_source():
+    """The weight-derived caches that are built on the host -- Swin's gathered relative-position bias, the decoder's key / value views of in_proj, the
+    PatchEmbed projection as a Linear view, the stacked sampling Linear of MSDeformAttn and the pixel decoder's 1x1-convolution views -- are rebuilt when any
+    of their sources is edited in place or replaced, and equal a fresh derivation."""
+    from rba_amd.modeling.pixel_decoder.msdeformattn import _cached_linear_view
+    model, a = _cpu_model("tiny1")
+    mods = dict(model.named_modules())
+    attn = mods["backbone.layers.0.blocks.1.attn"]
+    N = attn.window_size ** 2
+
+    def check_bias():
+        b, frag = attn.gathered_bias()
+        t, idx = attn.relative_position_bias_table, attn.relative_position_index
+        return frag is None and torch.equal(b, t[idx.view(-1)].view(N, N, -1).permute(2, 0, 1))
+
+    mha = mods["sem_seg_head.predictor.transformer_cross_attention_layers.0.multihead_attn"]
+    E = mha.embed_dim
+
+    def check_kv():
+        lk, lv = mha._kv_views()
+        w, b = mha.in_proj_weight, mha.in_proj_bias
+        return (torch.equal(lk.weight, w[E:2 * E]) and torch.equal(lk.bias, b[E:2 * E]) and torch.equal(lv.weight, w[2 * E:])
+                and torch.equal(lv.bias, b[2 * E:]))
+
+    pe = model.backbone.patch_embed
+
+    def check_pe():
+        v = pe._linear_view()
+        return torch.equal(v.weight, pe.proj.weight.reshape(pe.proj.weight.shape[0], -1)) and torch.equal(v.bias, pe.proj.bias)
+
+    msda = mods["sem_seg_head.pixel_decoder.transformer.encoder.layers.0.self_attn"]
+
+    def check_sampling():
+        lin = msda._sampling_linear()
+        so, aw = msda.sampling_offsets, msda.attention_weights
+        return torch.equal(lin.weight, torch.cat([so.weight, aw.weight])) and torch.equal(lin.bias, torch.cat([so.bias, aw.bias]))
+
+    conv = model.sem_seg_head.pixel_decoder.mask_features
+
+    def check_conv_view():
+        v = _cached_linear_view(conv)
+        return torch.equal(v.weight, conv.weight.view(conv.weight.shape[0], -1)) and torch.equal(v.bias, conv.bias)
+
+    cases = [(check_bias, _edits(attn, "relative_position_bias_table")
+              + [("index in place", lambda: attn.relative_position_index.copy_(attn.relative_position_index.flip(0).clone())),
+                 ("index replaced", lambda: setattr(attn, "relative_position_index", attn.relative_position_index.flip(1).clone()))]),
+             (check_kv, _edits(mha, "in_proj_weight") + _edits(mha, "in_proj_bias")),
+             (check_pe, _edits(pe.proj, "weight") + _edits(pe.proj, "bias")),
+             (check_sampling, _edits(msda.sampling_offsets, "weight") + _edits(msda.sampling_offsets, "bias")
+              + _edits(msda.attention_weights, "weight") + _edits(msda.attention_weights, "bias")),
+             (check_conv_view, _edits(conv, "weight") + _edits(conv, "bias"))]
+    with torch.no_grad():
+        for check, edits in cases:
+            assert check(), check.__name__
+            for what, edit in edits:
+                edit()
+                assert check(), (check.__name__, what)
