@@ -16,6 +16,9 @@
  *   rba_ms_deform_attn_fwd_f32  <- MultiScaleDeformableAttention.ms_deform_attn_forward
  *                                  (pixel_decoder/ops/src/vision.cpp:19, ops/src/ms_deform_attn.h:25-44,
  *                                   ops/src/cuda/ms_deform_attn_cuda.cu:25-85, ms_deform_im2col_cuda.cuh:242-304,928-959)
+ *   rba_ms_deform_attn_bwd_f32  <- MultiScaleDeformableAttention.ms_deform_attn_backward
+ *                                  (pixel_decoder/ops/src/vision.cpp:20, ops/src/ms_deform_attn.h:46-66,
+ *                                   ops/src/cuda/ms_deform_attn_cuda.cu:88-158)
  *   rba_reduce_f32              <- MaskFormer.semantic_inference (mask2former/maskformer_model.py:381-386)
  *                                  + get_RbA (evaluate_ood.py:143-150) + argmax (support.py:385-388)
  *   rba_reduce_up4_f32          <- the same preceded by the x4 mask upsample (maskformer_model.py:294-299)
@@ -99,6 +102,24 @@ int rba_ms_deform_attn_fwd_f32(const float* value, const int64_t* spatial_shapes
  * ops/test.py:35-47 checks the double path first).  Same shapes and checks; generic kernel. */
 int rba_ms_deform_attn_fwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                const double* sampling_loc, const double* attn_weight, double* out,
+                               int N, int S, int M, int D, int L, int Lq, int P, void* stream);
+
+/* K2 backward.  Gradients of the op above with respect to value, sampling_loc and attn_weight, given grad_out [N,Lq,M*D]
+ * (replaces MultiScaleDeformableAttention.ms_deform_attn_backward: pixel_decoder/ops/src/vision.cpp:20, ops/src/ms_deform_attn.h:46-66,
+ * ops/src/cuda/ms_deform_attn_cuda.cu:88-158).  Inputs as the forward; grad_value [N,S,M,D], grad_sampling_loc [N,Lq,M,L,P,2],
+ * grad_attn_weight [N,Lq,M,L,P].  On return (stream order) all three outputs are fully defined whatever they held before: grad_value is
+ * zero-filled here (hipMemsetAsync on `stream`) and then summed with float atomics -- its last bits depend on arrival order and may differ
+ * from launch to launch; the other two are written element by element with plain stores and are bitwise reproducible.  A sample outside the
+ * window (h <= -1, h >= H_l, w <= -1 or w >= W_l) gets exactly 0 in grad_sampling_loc and grad_attn_weight.  N == 0 or Lq == 0: success
+ * without a kernel launch (grad_value still zero-filled when it has elements). */
+int rba_ms_deform_attn_bwd_f32(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                               const float* sampling_loc, const float* attn_weight, const float* grad_out,
+                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight,
+                               int N, int S, int M, int D, int L, int Lq, int P, void* stream);
+/* The same in double precision (the reference dispatches both; its gradient test, ops/test.py:66-89, runs in double).  Generic kernel. */
+int rba_ms_deform_attn_bwd_f64(const double* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                               const double* sampling_loc, const double* attn_weight, const double* grad_out,
+                               double* grad_value, double* grad_sampling_loc, double* grad_attn_weight,
                                int N, int S, int M, int D, int L, int Lq, int P, void* stream);
 
 /* The sampling parameters of MSDeformAttn.forward in one pass (pixel_decoder/ops/modules/ms_deform_attn.py:95-115):

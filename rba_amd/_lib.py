@@ -27,6 +27,8 @@ SIGNATURES = {
     "rba_resample_bilinear_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_ms_deform_attn_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_ms_deform_attn_fwd_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "rba_ms_deform_attn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "rba_ms_deform_attn_bwd_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_msda_prepare_f32": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp],
     "rba_resample_bilinear_nhwc_gn_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _vp],
     "rba_group_norm_nhwc_stats_f32": [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp],
@@ -95,7 +97,7 @@ class TokenLinearProblem(ctypes.Structure):
                 ("N", ctypes.c_int), ("ld_out", ctypes.c_int), ("act", ctypes.c_int)]
 
 
-EXPECTED_ABI = 190        # rba_hip_version() the argtypes above were written for (include/rba_hip.h)
+EXPECTED_ABI = 191        # rba_hip_version() the argtypes above were written for (include/rba_hip.h)
 
 _lib = None
 

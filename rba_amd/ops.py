@@ -195,6 +195,46 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
 
 
 @_hip_op
+def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, grad_output,
+                            im2col_step=128):
+    """K2 backward.  Same signature and checks as MultiScaleDeformableAttention.ms_deform_attn_backward
+    (pixel_decoder/ops/functions/ms_deform_attn_func.py:43-49, ops/src/cuda/ms_deform_attn_cuda.cu:88-158): the forward's five
+    tensors and grad_output [N,Lq,M*D] -> (grad_value [N,S,M,D], grad_sampling_loc [N,Lq,M,L,P,2], grad_attn_weight [N,Lq,M,L,P]).
+    grad_value is summed with float atomics (last bits may differ between launches); the other two are bitwise reproducible.
+    `im2col_step` is only validated."""
+    lib = _lib.load()
+    dt = value.dtype if isinstance(value, torch.Tensor) and value.dtype == torch.float64 else torch.float32
+    _chk(value, "value", dt, dim=4)
+    _chk(spatial_shapes, "spatial_shapes", torch.int64, 2)
+    _chk(level_start_index, "level_start_index", torch.int64, 1)
+    _chk(sampling_locations, "sampling_loc", dt, dim=6)
+    _chk(attention_weights, "attn_weight", dt, dim=5)
+    _chk(grad_output, "grad_output", dt, dim=3)
+    N, S, M, D = value.shape
+    _, Lq, M2, L, P, two = sampling_locations.shape
+    if M2 != M or two != 2 or sampling_locations.shape[0] != N:
+        raise RbaHipError("sampling_loc shape does not match value")
+    if tuple(attention_weights.shape) != (N, Lq, M, L, P):
+        raise RbaHipError("attn_weight shape does not match sampling_loc")
+    if spatial_shapes.shape[0] != L or level_start_index.shape[0] != L:
+        raise RbaHipError("spatial_shapes / level_start_index must have L rows")
+    if tuple(grad_output.shape) != (N, Lq, M * D):
+        raise RbaHipError(f"grad_output must have shape {(N, Lq, M * D)}, got {tuple(grad_output.shape)}")
+    step = min(N, int(im2col_step))
+    if N > 0 and N % step != 0:
+        raise RbaHipError(f"batch({N}) must divide im2col_step({step})")
+    dev = value.device
+    grad_value = torch.empty((N, S, M, D), dtype=dt, device=dev)
+    grad_loc = torch.empty((N, Lq, M, L, P, 2), dtype=dt, device=dev)
+    grad_attn = torch.empty((N, Lq, M, L, P), dtype=dt, device=dev)
+    fn, name = ((lib.rba_ms_deform_attn_bwd_f64, "rba_ms_deform_attn_bwd_f64") if dt == torch.float64 else
+                (lib.rba_ms_deform_attn_bwd_f32, "rba_ms_deform_attn_bwd_f32"))
+    _lib.check(fn(_p(value), _p(spatial_shapes), _p(level_start_index), _p(sampling_locations), _p(attention_weights), _p(grad_output),
+                  _p(grad_value), _p(grad_loc), _p(grad_attn), N, S, M, D, L, Lq, P, _stream()), name)
+    return grad_value, grad_loc, grad_attn
+
+
+@_hip_op
 def masked_xattn(q, k, v, mask_logits=None, split_keys=None):
     """K3.  q [B,Q,nH,hd] (unscaled), k, v [B,S,nH,hd], mask_logits [B,Q,S] | None -> [B,Q,nH*hd].
     split_keys: use the split-key matrix-pipe path (needs a scratch buffer, allocated here); None = automatic
