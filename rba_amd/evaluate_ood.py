@@ -14,6 +14,7 @@ import torch
 from .arch import arch_from_cfg
 from .checkpoint import load_checkpoint
 from .config import load_cfg
+from .graph_replay import capture
 from .registry import META_ARCH_REGISTRY
 from . import maskformer_model as _mm  # noqa: F401  (registers MaskFormer)
 
@@ -156,16 +157,10 @@ class GraphedScore:
             return self.score_func(self.model, x[None])
         if entry is None:
             try:
-                static_in = x.clone()
-                g = torch.cuda.CUDAGraph()
                 if self.capture_stream is None:
                     self.capture_stream = torch.cuda.Stream(device=x.device)
-                self.capture_stream.wait_stream(torch.cuda.current_stream(x.device))
-                # captured on this object's own stream, replayed on self.stream; thread_local: the decode threads pin memory meanwhile
-                with torch.cuda.graph(g, stream=self.capture_stream, capture_error_mode="thread_local"):
-                    static_out = self.score_func(self.model, static_in[None])
-                torch.cuda.current_stream(x.device).wait_stream(self.capture_stream)
-                entry = self.graphs[key] = (g, static_in, static_out)
+                # captured on this object's own stream, replayed on self.stream; thread_local (capture): the decode threads pin memory meanwhile
+                entry = self.graphs[key] = capture(lambda s: self.score_func(self.model, s[None]), x, self.capture_stream)
             except Exception as e:                                   # noqa: BLE001 -- an optimisation only
                 print(f"[rba_amd] hipGraph capture failed for shape {key} ({type(e).__name__}: {e}); eager launches", file=sys.stderr)
                 torch.cuda.synchronize()

@@ -14,6 +14,8 @@ import torch.nn.functional as F
 from . import ops
 from .h2d import to_device
 from .arch import backbone_name as _backbone_name, complete
+from .graph_replay import GraphKey, GraphReplay, capture
+from .lru import ShapeCache
 from .modeling.backbone import resnet as _resnet  # noqa: F401  (registers build_resnet_backbone)
 from .modeling.backbone import swin as _swin  # noqa: F401  (registers D2SwinTransformer)
 from .modeling.meta_arch import mask_former_head as _head  # noqa: F401
@@ -237,10 +239,14 @@ class MaskFormer(nn.Module):
     LAUNCH_BOUND_RATIO = 0.95      # graph_replay = "auto": capture a shape when host issue time >= this fraction of the GPU span of an eager forward
     GRAPH_REMEASURE_EVERY = 32     # ... and measure a GPU-bound shape again after this many eager calls
 
+    def _replay_state(self):
+        """the one transient home of everything graph replay remembers (graph_replay.GraphReplay); never copied or pickled"""
+        return self.__dict__.get("_replay") or self.__dict__.setdefault("_replay", GraphReplay())
+
     def graph_decisions(self):
         """graph_replay = "auto": {(image shape, dtype, return_argmax, score): {"decision": "eager" | "replay", "host_issue_ms", "gpu_span_ms"}} of the last
         measurement of every shape met so far (bench.py reports it; tests assert on it)"""
-        return dict(self.__dict__.get("_graph_decisions", {}))
+        return dict(self._replay_state().decisions)
 
     def _measured_eager(self, key, batched_inputs, return_argmax, score):
         import time
@@ -250,9 +256,7 @@ class MaskFormer(nn.Module):
         e0.record(torch.cuda.current_stream(dev))
         out = self._rba_scores_eager(batched_inputs, return_argmax, score)
         e1.record(torch.cuda.current_stream(dev))
-        seen = self.__dict__.setdefault("_graph_seen", {})
-        if key in seen:
-            seen[key] = (time.perf_counter() - t0, e0, e1)
+        self._replay_state().measured(key, time.perf_counter() - t0, e0, e1)
         return out
 
     def _weights_version(self):
@@ -279,30 +283,27 @@ class MaskFormer(nn.Module):
         return st[1], v
 
     def _graph_key(self, image, return_argmax, score):
-        return (tuple(image.shape), image.dtype, image.device, torch.cuda.current_stream(image.device).cuda_stream, bool(return_argmax), score,
-                self.fused_upsample, self.fused_front_end, ops.SPLIT_MODE, ops.SPLIT_ACTIVATIONS, ops.TILES_MIN, ops.MLP_FUSED_MIN_ROWS, ops.concurrent_streams(),
-                ops.SWIN_ATTN_FUSED,
-                getattr(self.sem_seg_head.predictor, "sparse_intermediate_heads", None), self._weights_version())
+        return GraphKey(tuple(image.shape), image.dtype, image.device, torch.cuda.current_stream(image.device).cuda_stream, bool(return_argmax), score,
+                        self.fused_upsample, self.fused_front_end, ops.SPLIT_MODE, ops.SPLIT_ACTIVATIONS, ops.TILES_MIN, ops.MLP_FUSED_MIN_ROWS,
+                        ops.concurrent_streams(), ops.SWIN_ATTN_FUSED,
+                        getattr(self.sem_seg_head.predictor, "sparse_intermediate_heads", None), self._weights_version())
 
     def drop_graphs(self, release_constants=False):
         """Forget every captured graph (their pools are freed); the next calls run eagerly, then capture again.  release_constants: also
         un-pin the per-shape constants captures have read (lru.ShapeCache) -- only safe when no graph captured OUTSIDE the model (bench.py,
         evaluate_ood.GraphedScore) is still alive, e.g. after a device move."""
         if release_constants:
-            from .lru import ShapeCache
             for m_ in self.modules():
                 for v_ in vars(m_).values():
                     if isinstance(v_, ShapeCache):
                         v_.unpin()
-        self.__dict__.pop("_graphs", None)
-        self.__dict__.pop("_graph_seen", None)
-        self.__dict__.pop("_graph_thrash", None)
-        self.__dict__.pop("_graph_probe", None)
-        self.__dict__.pop("_graph_eager_fast", None)
+        self._replay_state().drop()
+
+    _TRANSIENT = ("_replay", "_param_flat")       # hipGraphs / events cannot be copied or pickled; a copy captures its own
 
     def __getstate__(self):
         st = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
-        for k in ("_graphs", "_graph_seen", "_graph_thrash", "_graph_probe", "_graph_decisions", "_graph_eager_fast", "_param_flat"):       # hipGraphs / events cannot be copied or pickled; a copy captures its own
+        for k in self._TRANSIENT:
             st.pop(k, None)
         return st
 
@@ -312,7 +313,7 @@ class MaskFormer(nn.Module):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k not in ("_graphs", "_graph_seen", "_graph_thrash", "_graph_probe", "_graph_decisions", "_graph_eager_fast", "_param_flat"):
+            if k not in self._TRANSIENT:
                 new.__dict__[k] = copy.deepcopy(v, memo)
         return new
 
@@ -322,86 +323,36 @@ class MaskFormer(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     def _graphed_scores(self, image, return_argmax, score):
-        """One batch-1 image (already on the device) -> (rba, argmax | None), replayed from a hipGraph captured per (image shape, dtype,
-        stream, outputs, arithmetic mode, weight version).  A forward is ~330 kernel launches that take the Python thread 6-7 ms to
-        issue against ~8 ms of GPU time; a caller that waits for every score (the reference's loop does: `.cpu()` per image,
-        support.py:375) therefore pays both in series.  The first call of a key runs eagerly (per-shape constants, weight planes), the
-        second captures, later ones copy the image into the graph's input and replay it on the CURRENT stream; the result is a fresh
-        tensor.  Returns None when the capture failed (the caller then runs eagerly; the failure is remembered for the key)."""
-        graphs = self.__dict__.setdefault("_graphs", {})
-        seen = self.__dict__.setdefault("_graph_seen", {})        # keys met once, not captured yet: bounded on its own, never evicts a graph
+        """One batch-1 image (already on the device) -> (rba, argmax | None), replayed from a hipGraph captured per GraphKey (image shape, dtype, stream,
+        outputs, arithmetic mode, weight version ...).  A forward is ~330 kernel launches that take the Python thread 6-7 ms to issue against ~8 ms of GPU
+        time; a caller that waits for every score (the reference's loop does: `.cpu()` per image, support.py:375) pays both in series.  When and whether a key
+        is captured is GraphReplay.step's decision; a replay copies the image into the graph's input and runs on the CURRENT stream, the result is a fresh
+        tensor.  Returns None when the caller is to run eagerly, and the key when that eager run is the one to be measured (_measured_eager)."""
+        state = self._replay_state()
         key = self._graph_key(image, return_argmax, score)
-        entry = graphs.get(key)
-        if entry is None:
-            if self.__dict__.get("_graph_thrash", 0) >= self.GRAPH_THRASH_MAX:
-                return None                                     # image shapes churn faster than graphs are replayed: stay eager (see below)
-            if key not in seen:
-                seen[key] = True
-                while len(seen) > 4 * self.GRAPH_MAX:
-                    seen.pop(next(iter(seen)))
-                return None
-            if self.graph_replay == "auto":
-                # measured policy (round 6).  Call 1 of a key ran eagerly (lazy initialisation); call 2 runs eagerly between two HIP events with the host's issue
-                # time taken beside them (rba_scores -> _measured_eager); call 3 reads the pair: the forward is LAUNCH-BOUND when the Python thread needed at
-                # least LAUNCH_BOUND_RATIO of the GPU's own span to issue it (a launch-bound GPU span stretches to the issue time, so the ratio saturates
-                # near 1) -- then, and only then, the shape is captured.  A GPU-bound shape stays eager and is measured again every GRAPH_REMEASURE_EVERY
-                # calls (the host may get busier: decode threads, other ranks).
-                st = seen[key]
-                if st is True or (isinstance(st, int) and st <= 0):
-                    self.__dict__["_graph_probe"] = key
-                    return None
-                if isinstance(st, int):
-                    seen[key] = st - 1
-                    return None
-                t_issue, e0, e1 = st
-                e1.synchronize()
-                t_gpu = e0.elapsed_time(e1) * 1e-3
-                bound = t_issue >= self.LAUNCH_BOUND_RATIO * t_gpu
-                self.__dict__.setdefault("_graph_decisions", {})[key[:2] + key[4:6]] = {
-                    "decision": "replay" if bound else "eager", "host_issue_ms": t_issue * 1e3, "gpu_span_ms": t_gpu * 1e3}
-                if not bound:
-                    seen[key] = 0                                   # the next slow-path call of this key is a measurement again ...
-                    fast = self.__dict__.setdefault("_graph_eager_fast", {})
-                    while len(fast) > 4 * self.GRAPH_MAX:
-                        fast.pop(next(iter(fast)))
-                    # ... and rba_scores serves the next GRAPH_REMEASURE_EVERY calls of the shape eagerly before it asks again
-                    fast[(key[0], key[1], key[4], key[5], key[8], key[3])] = self.GRAPH_REMEASURE_EVERY
-                    return None
-            del seen[key]
-            entry = "seen"
-            while len(graphs) >= self.GRAPH_MAX:                # oldest first; a graph owns its pool, dropping it frees the memory
-                old = graphs.pop(next(iter(graphs)))            # (on ROCm destroying a graph synchronises the device)
-                if isinstance(old, tuple) and old[4][0] <= 1:             # 1 = only the replay that followed its capture
-                    # a graph that was never replayed is being evicted: with more live shapes than GRAPH_MAX every capture costs more than it
-                    # saves; after GRAPH_THRASH_MAX of these the model stops capturing new keys (drop_graphs() resets)
-                    self.__dict__["_graph_thrash"] = self.__dict__.get("_graph_thrash", 0) + 1
-        if entry == "seen":
+        what = state.step(key, self.graph_replay == "auto", self)
+        if what == "measure":
+            return key
+        if what == "capture":
             try:
-                static_in = image.clone()
                 cap = torch.cuda.Stream(device=image.device)       # its own capture stream: per-stream state (K1's tile counter) is this graph's alone
-                cap.wait_stream(torch.cuda.current_stream(image.device))
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=cap, capture_error_mode="thread_local"):
-                    r = self._rba_scores_eager([{"image": static_in}], return_argmax, score)[0]
-                torch.cuda.current_stream(image.device).wait_stream(cap)
-                entry = graphs[key] = (g, static_in, r, cap, [0])
+                state.captured(key, *capture(lambda x: self._rba_scores_eager([{"image": x}], return_argmax, score)[0], image, cap), stream=cap)
             except Exception as e:                                   # noqa: BLE001 -- an optimisation only
                 import sys
                 print(f"[rba_amd] hipGraph capture failed for image shape {tuple(image.shape)} ({type(e).__name__}: {e}); eager launches",
                       file=sys.stderr)
                 torch.cuda.synchronize(image.device)
-                entry = graphs[key] = False
-        if entry is False:
+                state.captured(key)
+        rec = state.graphs.get(key) if what in ("replay", "capture") else None
+        if rec is None or rec.state != "captured":
             return None
-        graphs[key] = graphs.pop(key)                               # most recently used last
-        g, static_in, r, _, uses = entry
-        uses[0] += 1
-        static_in.copy_(image, non_blocking=True)
-        g.replay()
+        rec.static_in.copy_(image, non_blocking=True)
+        rec.graph.replay()
+        r = rec.static_out
         return (r[0].clone(), r[1].clone()) if return_argmax else r.clone()
 
     def live_graphs(self):
-        return sum(1 for e in self.__dict__.get("_graphs", {}).values() if isinstance(e, tuple))
+        return self._replay_state().live()
 
     @torch.no_grad()
     def rba_scores(self, batched_inputs, return_argmax=False, score="rba"):
@@ -416,23 +367,22 @@ class MaskFormer(nn.Module):
             if torch.is_tensor(image) and image.dim() == 3 and image.dtype in (torch.uint8, torch.float32) \
                     and set(batched_inputs[0]) <= {"image"}:
                 image = to_device(image, self.device).contiguous()
+                batched_inputs = [{"image": image}]
                 if self.graph_replay == "auto":
                     # a shape measured to be GPU-bound stays eager for GRAPH_REMEASURE_EVERY calls without even building the graph key (the key walks every
                     # parameter's version: host time in front of the image's first launch, which the serial caller pays in full).  A stale entry costs
                     # speed only -- eager launches are always right.
-                    fast = self.__dict__.setdefault("_graph_eager_fast", {})
+                    fast = self._replay_state().eager_left
                     fk = (tuple(image.shape), image.dtype, bool(return_argmax), score, ops.SPLIT_MODE, torch.cuda.current_stream(image.device).cuda_stream)
                     left = fast.get(fk, 0)
                     if left > 0:
                         fast[fk] = left - 1
-                        return self._rba_scores_eager([{"image": image}], return_argmax, score)
+                        return self._rba_scores_eager(batched_inputs, return_argmax, score)
                 r = self._graphed_scores(image, return_argmax, score)
+                if isinstance(r, GraphKey):                     # graph_replay = "auto": this eager call is the one that is measured
+                    return self._measured_eager(r, batched_inputs, return_argmax, score)
                 if r is not None:
                     return [r]
-                batched_inputs = [{"image": image}]
-                probe = self.__dict__.pop("_graph_probe", None)
-                if probe is not None:                          # graph_replay = "auto": this eager call is the one that is measured
-                    return self._measured_eager(probe, batched_inputs, return_argmax, score)
         return self._rba_scores_eager(batched_inputs, return_argmax, score)
 
     @torch.no_grad()

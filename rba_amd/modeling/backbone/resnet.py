@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ...lru import derived
 from ...registry import BACKBONE_REGISTRY
 
 STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -29,18 +30,18 @@ class ConvBN(nn.Module):
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
         self.norm = nn.BatchNorm2d(cout)
         self.stride, self.padding = stride, padding
-        self._folded = None
 
     def folded(self):
         """(weight * scale, bias - running_mean * scale) with scale = norm.weight / sqrt(running_var + eps): rebuilt when any of the five sources
-        is edited in place or replaced (key: data pointer and version of each)"""
+        is edited in place or replaced"""
         n = self.norm
-        key = (self.weight.device,) + tuple((t.data_ptr(), t._version) for t in (self.weight, n.weight, n.bias, n.running_mean, n.running_var))
-        if self._folded is None or self._folded[0] != key:
+
+        def build():
             scale = n.weight * torch.rsqrt(n.running_var + n.eps)
             w = (self.weight * scale.view(-1, 1, 1, 1)).contiguous(memory_format=torch.channels_last)
-            self._folded = (key, w, (n.bias - n.running_mean * scale).contiguous())
-        return self._folded[1], self._folded[2]
+            return w, (n.bias - n.running_mean * scale).contiguous()
+
+        return derived(self, "folded", (self.weight, n.weight, n.bias, n.running_mean, n.running_var), build)
 
     def forward(self, x, relu=False):
         w, b = self.folded()

@@ -8,11 +8,14 @@ K5) reading the un-padded qkv tensor; dense projections are the repository's f16
 (``ops.swin_attn_block``: C = 128; ``ops.swin_attn_qkv``: C = 128 / 192 / 256) the attention half of a block -- norm1, qkv, attention[, proj, residual] --
 is one launch per block, and the C = 128 MLP computes norm2 itself (``ops.mlp_fused_ln``).
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
+from ...lru import derived
 from ...registry import BACKBONE_REGISTRY
 
 
@@ -34,27 +37,22 @@ class WindowAttention(nn.Module):
         self.register_buffer("relative_position_index", relative_position_index(window_size))
         self.qkv = nn.Linear(dim, dim * 3)
         self.proj = nn.Linear(dim, dim)
-        self._bias_cache = None
-        self._block_image = None
 
     def block_image(self):
         """K7's packed qkv + proj weights (ops.swin_attn_block_weights), once per weight load."""
         wq, wp = self.qkv.weight, self.proj.weight
-        key = (wq.data_ptr(), wq._version, wp.data_ptr(), wp._version, wq.device)
-        if self._block_image is None or self._block_image[0] != key:
-            self._block_image = (key, ops.swin_attn_block_weights(wq.detach().contiguous(), wp.detach().contiguous()))
-        return self._block_image[1]
+        return derived(self, "block_image", (wq, wp), lambda: ops.swin_attn_block_weights(wq.detach().contiguous(), wp.detach().contiguous()))
 
     def gathered_bias(self):
-        """[nH, N, N] relative-position bias (swin.py:148-155), gathered once per weight load."""
+        """[nH, N, N] relative-position bias (swin.py:148-155) and its K5 fragments (None off the GPU), gathered once per weight load."""
         t, idx = self.relative_position_bias_table, self.relative_position_index
-        key = (t.data_ptr(), t._version, t.device, idx.data_ptr(), idx._version)
-        if self._bias_cache is None or self._bias_cache[0] != key:
+
+        def build():
             N = self.window_size ** 2
             b = t[idx.view(-1)].view(N, N, -1).permute(2, 0, 1).contiguous()
-            frag = ops.swin_bias_fragments(b, self.window_size) if b.is_cuda else None
-            self._bias_cache = (key, b, frag)
-        return self._bias_cache[1], self._bias_cache[2]
+            return b, ops.swin_bias_fragments(b, self.window_size) if b.is_cuda else None
+
+        return derived(self, "gathered_bias", (t, idx), build)
 
 
 class Mlp(nn.Module):
@@ -185,13 +183,8 @@ class PatchEmbed(nn.Module):
 
     def _linear_view(self):
         """proj as an nn.Linear over the patch's 3 ps^2 values (weight [C, 3 ps^2] view, bias), cached per weight load"""
-        w, b = self.proj.weight, self.proj.bias
-        key = (w.data_ptr(), w._version, w.device, None if b is None else b.data_ptr())      # the view holds the bias OBJECT: a replaced bias is a new key
-        c = getattr(self, "_rba_lin", None)
-        if c is None or c[0] != key:
-            from types import SimpleNamespace
-            c = self._rba_lin = (key, SimpleNamespace(weight=w.detach().reshape(w.shape[0], -1), bias=b))
-        return c[1]
+        w, b = self.proj.weight, self.proj.bias       # the view holds the bias OBJECT: a replaced bias is a new key
+        return derived(self, "linear_view", (w, b), lambda: SimpleNamespace(weight=w.detach().reshape(w.shape[0], -1), bias=b))
 
     def fused_ok(self):
         w = self.proj.weight
@@ -202,16 +195,16 @@ class PatchEmbed(nn.Module):
         4x4 convolution in ONE kernel (ops.patch_im2col), the projection as an f16x3 GEMM over K = 48 (+16 zero columns), then the
         LayerNorm -- instead of five elementwise passes, a library convolution and a 67 MB NCHW -> token-major copy."""
         w = self.proj.weight
-        key = (w.data_ptr(), w._version, w.device)
-        cache = getattr(self, "_rba_planes", None)
-        if cache is None or cache[0] != key:
+
+        def build():
             w64 = torch.zeros((w.shape[0], 64), dtype=torch.float32, device=w.device)
             w64[:, :48] = w.detach().reshape(w.shape[0], 48)
-            cache = (key, ops.split_weight(w64, mode="f16x3"))
-            self._rba_planes = cache
+            return ops.split_weight(w64, mode="f16x3")
+
+        planes = derived(self, "planes64", (w,), build)
         cols = torch.stack([ops.patch_im2col(im, mean, std, Hp, Wp) for im in images]) if len(images) > 1 \
             else ops.patch_im2col(images[0], mean, std, Hp, Wp)[None]
-        x = ops.split_linear(cols, cache[1], self.proj.bias, out_features=w.shape[0])
+        x = ops.split_linear(cols, planes, self.proj.bias, out_features=w.shape[0])
         return ops.add_layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)[1], Hp // 4, Wp // 4
 
 

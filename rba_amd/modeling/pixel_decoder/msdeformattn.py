@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 from ... import ops
 from ...arch import FEATURE_NAMES, feature_channels, num_fpn_levels
-from ...lru import ShapeCache
+from ...lru import ShapeCache, derived, source_key
 from ...registry import SEM_SEG_HEADS_REGISTRY
 from ..transformer_decoder.position_encoding import PositionEmbeddingSine
 from .ops.ms_deform_attn import MSDeformAttn
@@ -27,13 +27,14 @@ class _LinearView:
 
 def _cached_linear_view(mod):
     """The nn.Linear view of a 1x1 convolution module, cached on the module per weight load."""
-    w, b = mod.weight, mod.bias
-    key = (w.data_ptr(), w._version, w.device, None if b is None else b.data_ptr())      # the view holds the bias OBJECT: a replaced bias is a new key
-    c = getattr(mod, "_rba_lin", None)
-    if c is None or c[0] != key:
-        c = (key, _LinearView(w.view(w.shape[0], -1), mod.bias))
-        mod._rba_lin = c
-    return c[1]
+    w, b = mod.weight, mod.bias                    # the view holds the bias OBJECT: a replaced bias is a new key
+    return derived(mod, "linear_view", (w, b), lambda: _LinearView(w.view(w.shape[0], -1), b))
+
+
+def _conv3x3_planes(mod):
+    """ops.conv3x3_weight of a 3x3 convolution module, one entry PER arithmetic mode: a bf16x6 re-score does not evict the f16x3 planes"""
+    w = mod.weight
+    return derived(mod, ("conv3x3", ops.SPLIT_MODE), (w, mod.bias), lambda: ops.conv3x3_weight(w.detach()))
 
 
 def _conv1x1_nchw(x, mod):
@@ -63,13 +64,7 @@ class ConvNorm(nn.Module):
         elif self.weight.shape[1] % 32 == 0:
             # round 5: the NCHW fallback layout's 3 x 3 convolutions run the library's own implicit-GEMM kernel too (one transpose in, one out): MIOpen -- the
             # one component that ever returned different bits from one call to the next (profiles/r04_flake_cause.txt) -- is out of the product
-            w = self.weight
-            key = (w.data_ptr(), w._version, w.device)
-            cache = self.__dict__.setdefault("_rba_conv3", {})                    # one entry PER arithmetic mode: a bf16x6 re-score does not evict the f16x3 planes
-            c = cache.get(ops.SPLIT_MODE)
-            if c is None or c[0] != key:
-                c = cache[ops.SPLIT_MODE] = (key, ops.conv3x3_weight(w.detach()))
-            y = ops.conv3x3_nhwc(x.permute(0, 2, 3, 1).contiguous(), c[1], self.bias, out_features=w.shape[0])
+            y = ops.conv3x3_nhwc(x.permute(0, 2, 3, 1).contiguous(), _conv3x3_planes(self), self.bias, out_features=self.weight.shape[0])
             x = y.permute(0, 3, 1, 2).contiguous()
         else:                                                                    # (no released configuration: conv_dim is 256)
             x = F.conv2d(x, self.weight, self.bias, padding=self.padding)
@@ -141,8 +136,7 @@ class MSDeformAttnTransformerEncoderOnly(nn.Module):
             p_ = torch.cat([p.flatten(2).transpose(1, 2) + self.level_embed[l].view(1, 1, -1) for l, p in enumerate(pos_embeds)], 1)
             return p_.expand(B, -1, -1).contiguous()
 
-        le = self.level_embed
-        pos = self._pos_cache.get((tuple(shapes), B, dev, le.data_ptr(), le._version), build_pos)
+        pos = self._pos_cache.get((tuple(shapes), B, dev, source_key(self.level_embed)), build_pos)
 
         def build():
             sh_ = torch.as_tensor(shapes, dtype=torch.long, device=dev)
@@ -192,19 +186,9 @@ class MSDeformAttnPixelDecoder(nn.Module):
         t = x.permute(0, 2, 3, 1)
         return t.reshape(x.shape[0], -1, x.shape[1]) if (x.is_cuda and x.dtype == torch.float32 and t.is_contiguous()) else None
 
-    @staticmethod
-    def _cached(mod, name, build):
-        w, b = mod.weight, getattr(mod, "bias", None)
-        key = (w.data_ptr(), w._version, w.device, None if b is None else b.data_ptr())  # views built here hold the bias OBJECT
-        c = getattr(mod, name, None)
-        if c is None or c[0] != key:
-            c = (key, build())
-            setattr(mod, name, c)
-        return c[1]
-
     def _conv1x1(self, tok, mod, use_bias=True):
         """1x1 convolution of `mod` (weight [N,C,1,1]) on tokens [B,P,C] -> [B,P,N]."""
-        lin = self._cached(mod, "_rba_lin", lambda: _LinearView(mod.weight.view(mod.weight.shape[0], -1), mod.bias))
+        lin = _cached_linear_view(mod)
         N, K = lin.weight.shape
         M = tok.numel() // K
         if not ops.split_linear_pays(M, N, K) and ops.token_linear_pays(M, N, K) and tok.is_contiguous():
@@ -245,8 +229,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
             lat_mr = None
             if fold and tok.is_contiguous() and ops.linear_emits_gn_moments(B * h * w, d, tok.shape[-1], h * w, 32):
                 # round 4: the lateral convolution's epilogue leaves the GroupNorm moments of its output -- no statistics pass over `lat`
-                lin = self._cached(ad, "_rba_lin", lambda: _LinearView(ad.weight.view(ad.weight.shape[0], -1), ad.bias))
-                lat, lat_mr = ops.linear_gn_stats(tok, lin, 32, ad.norm.eps, h * w, use_bias=False)
+                lat, lat_mr = ops.linear_gn_stats(tok, _cached_linear_view(ad), 32, ad.norm.eps, h * w, use_bias=False)
             else:
                 lat = self._conv1x1(tok, ad, use_bias=False)                               # raw lateral convolution [B, h*w, d]
             split = ops.conv3x3_takes_split(B * h * w, d) and d % 32 == 0
@@ -277,7 +260,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
                     ups = [ops.resample_bilinear_nhwc(prev[b].view(ph, pw, d), (h, w), add=cur[b].view(h, w, d))
                            for b in range(B)]                                                  # :357-358 fused sum
                     yy = ups[0][None] if B == 1 else torch.stack(ups)
-            planes = self._cached(ly, "_rba_conv_" + ops.SPLIT_MODE, lambda: ops.conv3x3_weight(ly.weight.detach()))    # per arithmetic form
+            planes = _conv3x3_planes(ly)
             last = idx == self.num_fpn_levels - 1                  # its GroupNorm is applied below, inside the mask-feature projection
             if fold and split and ops.conv3x3_emits_gn_moments(B, h, w, d, 32):
                 prev, mr = ops.conv3x3_nhwc_gn_stats(yy, planes, 32, ly.norm.eps, None, out_features=d)     # round 4: statistics from the convolution's epilogue
@@ -288,8 +271,8 @@ class MSDeformAttnPixelDecoder(nn.Module):
                 prev_norm = (ops.group_norm_nhwc_stats(prev, 32, ly.norm.eps) if fold and not last else None, ly.norm)
             ph, pw = h, w
         mfw = self.mask_features.weight
-        planes = self._cached(self.mask_features, "_rba_mf_planes_" + ops.SPLIT_MODE,           # per arithmetic form (f16x3 since round 3)
-                              lambda: ops.split_weight(mfw.detach().view(mfw.shape[0], -1).contiguous()))
+        planes = derived(self.mask_features, ("mf_planes", ops.SPLIT_MODE), (mfw, self.mask_features.bias),      # per arithmetic form (f16x3 since round 3)
+                         lambda: ops.split_weight(mfw.detach().view(mfw.shape[0], -1).contiguous()))
         if prev_norm is not None and fold and FOLD_MASK_FEATURE_NORM and ops.split_linear_nchw_out_takes_gn(planes, ph * pw, d, 32):
             # round 4: the last level's GroupNorm + ReLU feeds only the mask-feature projection (:357-362) -- applied inside that kernel's loads, the
             # normalised 1/4-resolution map (134 MB at 1024 x 2048) is never written or read back

@@ -3,6 +3,8 @@
 kernels K2 (forward and backward).  Difference by design: unlike the reference's bare ``except`` (ms_deform_attn.py:116-121)
 that silently falls back to grid_sample, a failure of the native op raises.  ``MSDeformAttn`` runs the fused inference path
 unless its ``differentiable`` attribute is set (see the class)."""
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -10,6 +12,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .... import ops
+from ....lru import derived
 
 
 class MSDeformAttnFunction(Function):
@@ -61,25 +64,18 @@ class MSDeformAttn(nn.Module):
     def _sampling_linear(self):
         """[sampling_offsets ; attention_weights] stacked along the output dimension, rebuilt when either weight changes."""
         so, aw = self.sampling_offsets, self.attention_weights
-        key = tuple((t.data_ptr(), t._version) for t in (so.weight, aw.weight, so.bias, aw.bias))
-        cache = getattr(self, "_rba_sampling", None)
-        if cache is None or cache[0] != key:
-            from types import SimpleNamespace
+
+        def build():
             lin = SimpleNamespace(weight=torch.cat([so.weight.detach(), aw.weight.detach()], 0).contiguous(),
                                   bias=torch.cat([so.bias.detach(), aw.bias.detach()], 0).contiguous())
-            cache = (key, lin)
-            self._rba_sampling = cache
-        return cache[1]
+            lin.parts = [(SimpleNamespace(weight=lin.weight[c:c + 256], bias=lin.bias[c:c + 256]), c) for c in range(0, lin.weight.shape[0], 256)]
+            return lin
+
+        return derived(self, "sampling_linear", (so.weight, aw.weight, so.bias, aw.bias), build)
 
     def _sampling_parts(self):
         """the stacked sampling Linear cut into row chunks of <= 256 outputs for the row-complete token kernel: [(linear view, first column)]"""
-        lin = self._sampling_linear()
-        parts = getattr(lin, "parts", None)
-        if parts is None:
-            from types import SimpleNamespace
-            n = lin.weight.shape[0]
-            parts = lin.parts = [(SimpleNamespace(weight=lin.weight[c:c + 256], bias=lin.bias[c:c + 256]), c) for c in range(0, n, 256)]
-        return parts
+        return self._sampling_linear().parts
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                 input_padding_mask=None, query_pos=None, post=None):

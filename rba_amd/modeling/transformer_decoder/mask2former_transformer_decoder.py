@@ -6,12 +6,14 @@ the ``sigmoid(mask) < 0.5`` threshold and the all-masked-row fix fused in (the b
 reference is never materialised); mask logits are the HIP kernel K4; the bilinear down-sample that feeds the
 attention mask is the HIP resampler.
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ...lru import ShapeCache
+from ...lru import ShapeCache, derived, source_key
 from ...registry import TRANSFORMER_DECODER_REGISTRY
 from .position_encoding import PositionEmbeddingSine
 
@@ -47,14 +49,9 @@ class _MHAParams(nn.Module):
 
     def _kv_views(self):
         """the key / value rows of in_proj as Linear views (their packed weight images are cached on the views)"""
-        w, b = self.in_proj_weight, self.in_proj_bias
-        key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
-        c = getattr(self, "_rba_kv", None)
-        if c is None or c[0] != key:
-            from types import SimpleNamespace
-            E = self.embed_dim
-            c = self._rba_kv = (key, SimpleNamespace(weight=w[E:2 * E], bias=b[E:2 * E]), SimpleNamespace(weight=w[2 * E:], bias=b[2 * E:]))
-        return c[1], c[2]
+        w, b, E = self.in_proj_weight, self.in_proj_bias, self.embed_dim
+        return derived(self, "kv_views", (w, b),
+                       lambda: (SimpleNamespace(weight=w[E:2 * E], bias=b[E:2 * E]), SimpleNamespace(weight=w[2 * E:], bias=b[2 * E:])))
 
     def forward(self, query, key, value, mask_logits=None, key_add=None, query_add=None):
         """batch-first: query [B,Q,E], key/value [B,S,E]; mask_logits [B,Q,S] (blocked iff sigmoid < 0.5).  key_add / query_add: the keys /
@@ -232,7 +229,7 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         ps = [self.query_feat.weight, self.decoder_norm.weight, self.decoder_norm.bias, self.class_embed.weight, self.class_embed.bias]
         for ly in self.mask_embed.layers:
             ps += [ly.weight, ly.bias]
-        key = (B, device, tuple((p_.data_ptr(), p_._version) for p_ in ps))
+        key = (B, device, source_key(*ps))
         cache = self.__dict__.get("_rba_heads0")
         if cache is None:
             cache = self.__dict__["_rba_heads0"] = ShapeCache(4)

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import RbaHipError
+from .lru import derived
 
 
 def _stream():
@@ -771,17 +772,13 @@ def linear(x, lin, use_bias=True, gelu=False, relu=False, residual=None, split_o
 def _cached_planes(lin, w, pad_k=None):
     """split_weight(w) of the current split mode, cached on the module per mode (the bf16x6 planes of the non-finite fallback stay
     beside the f16x3 ones: switching modes does not re-split).  pad_k: w zero-padded to that many columns first."""
-    key = (w.data_ptr(), w._version, w.device, pad_k)
-    caches = getattr(lin, "_rba_planes", None)
-    if not isinstance(caches, dict):
-        caches = lin._rba_planes = {}
-    cache = caches.get(_split_mode())
-    if cache is None or cache[0] != key:
+    def build():
         w2 = w.detach().contiguous()
         if pad_k is not None:
             w2 = torch.nn.functional.pad(w2, (0, pad_k - w2.shape[1]))
-        cache = caches[_split_mode()] = (key, split_weight(w2))
-    return cache[1]
+        return split_weight(w2)
+
+    return derived(lin, ("planes", _split_mode()), (w,), build, pad_k)
 
 
 @contextlib.contextmanager
@@ -1145,21 +1142,17 @@ def token_linear_pays(M, N, K):
 def _token_planes(lin):
     """fragment-ordered f16 (h, l) image of lin.weight, packed once per weight load and cached on the module"""
     w = lin.weight
-    key = (w.data_ptr(), w._version, w.device)
-    cache = getattr(lin, "_rba_token_planes", None)
-    if cache is None or cache[0] != key:
+
+    def build():
         lib = _lib.load()
         w2 = w.detach().contiguous()
         _chk(w2, "weight", dim=2)
         N, K = w2.shape
         packed = torch.empty((((N + 15) // 16) * (K // 32) * 128, 4), dtype=torch.int32, device=w.device)
         _lib.check(lib.rba_token_linear_pack_f16x2(_p(w2), _p(packed), N, K, _stream()), "rba_token_linear_pack_f16x2")
-        cache = (key, packed)
-        try:
-            lin._rba_token_planes = cache
-        except AttributeError:                      # objects with __slots__ (none today): no caching
-            pass
-    return cache[1]
+        return packed
+
+    return derived(lin, "token_planes", (w,), build)
 
 
 @_hip_op

@@ -697,10 +697,12 @@ def test_split_mode_switch_bf16x6_matches_f16x3(monkeypatch):
     assert ops.SPLIT_MODE == "f16x3"
     r3 = model.rba_scores([{"image": image}])[0].clone()
     fc1 = model.backbone.layers[2].blocks[0].mlp.fc1
-    assert fc1._rba_planes["f16x3"][1].dtype == torch.float16
+    from rba_amd.lru import peek
+    assert peek(fc1, ("planes", "f16x3")).dtype == torch.float16
     with ops.split_mode("bf16x6"):                                  # (per thread since round 5: set through the context manager, not by assignment)
         r6 = model.rba_scores([{"image": image}])[0]
-    assert fc1._rba_planes["bf16x6"][1].dtype == torch.bfloat16
+    assert peek(fc1, ("planes", "bf16x6")).dtype == torch.bfloat16
+    assert peek(fc1, ("planes", "f16x3")).dtype == torch.float16             # ... and the f16x3 planes are still beside them
     assert (r3 - r6).abs().max().item() < 5e-5
     assert ops.SPLIT_MODE == "f16x3"
     assert torch.equal(model.rba_scores([{"image": image}])[0], r3)
@@ -971,6 +973,9 @@ def test_model_with_captured_graphs_can_be_deep_copied_and_never_thrashes():
     assert torch.equal(model.rba_scores([{"image": im}])[0], want)
     twin = copy.deepcopy(model)
     assert twin.live_graphs() == 0 and model.live_graphs() == 1
+    from rba_amd.lru import _STORE
+    assert any(vars(m).get(_STORE) for m in model.modules())                # the original keeps its weight images; the twin starts without any
+    assert not any(vars(m).get(_STORE) for m in twin.modules())
     for _ in range(3):
         assert torch.equal(twin.rba_scores([{"image": im}])[0], want)
     assert twin.live_graphs() == 1
@@ -982,13 +987,13 @@ def test_model_with_captured_graphs_can_be_deep_copied_and_never_thrashes():
         x = torch.randint(0, 256, (3,) + hw, generator=g, dtype=torch.uint8).cuda()
         churn.rba_scores([{"image": x}])
         churn.rba_scores([{"image": x}])
-    assert churn.__dict__.get("_graph_thrash", 0) >= churn.GRAPH_THRASH_MAX and churn.live_graphs() <= churn.GRAPH_MAX
+    assert churn._replay_state().thrash >= churn.GRAPH_THRASH_MAX and churn.live_graphs() <= churn.GRAPH_MAX
     n_before = churn.live_graphs()
     x = torch.randint(0, 256, (3, 200, 64), generator=g, dtype=torch.uint8).cuda()
     churn.rba_scores([{"image": x}]); churn.rba_scores([{"image": x}]); churn.rba_scores([{"image": x}])
     assert churn.live_graphs() == n_before                                  # no new capture any more
     churn.drop_graphs()
-    assert churn.__dict__.get("_graph_thrash", 0) == 0
+    assert churn._replay_state().thrash == 0
 
 
 def test_model_zoo_check_tool_end_to_end(tmp_path, monkeypatch, capsys):
