@@ -96,3 +96,28 @@ __device__ __forceinline__ void rba_split_f16x2(float a, float b, uint32_t& h, u
   h = ap;
   l = r;
 }
+
+// The bf16x6 split arithmetic and activation shared by split_linear.hip and split_linear_dma.h: two fp32 -> one packed bf16 pair (rne; lowers to
+// v_cvt_pk_bf16_f32) and the halves of such a pair back as fp32.
+__device__ __forceinline__ uint32_t pack_bf16(float x0, float x1) {
+  typedef __bf16 rba_bf16x2 __attribute__((ext_vector_type(2)));
+  const rba_bf16x2 v = {(__bf16)x0, (__bf16)x1};
+  return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ float lo_as_f32(uint32_t pk) { return __uint_as_float(pk << 16); }
+__device__ __forceinline__ float hi_as_f32(uint32_t pk) { return __uint_as_float(pk & 0xffff0000u); }
+
+// Exact-form GELU 0.5 x (1 + erf(x / sqrt 2)) (nn.GELU default, swin.py:51) with erf from Abramowitz & Stegun 7.1.26
+// (|error| <= 1.5e-7, the size of fp32 erff's own rounding in this expression): 14 VALU instead of ocml erff's two-branch
+// ~45, which cost 20 % of the fc1 kernel when every lane evaluates 64 of them in the epilogue.
+__device__ __forceinline__ float gelu_erf(float v) {
+  const float x = fabsf(v) * 0.70710678118654752440f;
+  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, x, 1.0f));
+  float p = fmaf(1.061405429f, t, -1.453152027f);
+  p = fmaf(p, t, 1.421413741f);
+  p = fmaf(p, t, -0.284496736f);
+  p = fmaf(p, t, 0.254829592f);
+  const float e = p * t * __expf(-x * x);                       // 1 - erf(|x| / sqrt 2)
+  const float one_plus_erf = v >= 0.f ? 2.0f - e : e;
+  return 0.5f * v * one_plus_erf;
+}

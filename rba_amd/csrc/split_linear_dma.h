@@ -27,7 +27,6 @@
 namespace {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
@@ -37,13 +36,6 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // the counted vmcnt + barrier at the head of each super-stage.
 extern __shared__ __attribute__((aligned(16))) u32x4_t v4_lds[];
 extern __shared__ __attribute__((aligned(16))) u32x4_t v4_dma[];
-
-__device__ __forceinline__ uint32_t pack_bf16(float x0, float x1) {           // rne; lowers to v_cvt_pk_bf16_f32
-  bf16x2_t v = {(__bf16)x0, (__bf16)x1};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float lo_as_f32(uint32_t pk) { return __uint_as_float(pk << 16); }
-__device__ __forceinline__ float hi_as_f32(uint32_t pk) { return __uint_as_float(pk & 0xffff0000u); }
 
 // 8 fp32 (two 16-byte LDS reads) -> the three bf16x8 MFMA operands hi / mid / lo (x = hi + mid + lo exactly)
 __device__ __forceinline__ void split8(const f32x4 u, const f32x4 v, bf16x8_t& p0, bf16x8_t& p1, bf16x8_t& p2) {
@@ -64,18 +56,28 @@ __device__ __forceinline__ void split8(const f32x4 u, const f32x4 v, bf16x8_t& p
   p2 = __builtin_bit_cast(bf16x8_t, l);
 }
 
-// Exact-form GELU (nn.GELU default, swin.py:51), erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7): see split_linear.hip
-__device__ __forceinline__ float gelu_erf(float v) {
-  const float x = fabsf(v) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, x, 1.0f));
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float e = p * t * __expf(-x * x);
-  const float one_plus_erf = v >= 0.f ? 2.0f - e : e;
-  return 0.5f * v * one_plus_erf;
+// Prologue and epilogue of the GEMM-shaped entry points (split_linear_dma.hip, split_linear_gnf.hip).  An entry point first checks what only it knows about
+// its sizes, then RBA_GEMM_PROLOGUE(M, K, nonempty_ok, pointers...): M >= 0 and K (the operand's channel count) a positive multiple of 32; an empty call
+// (M == 0) returns 0 before any pointer is looked at; nonempty_ok = what only a call with rows must meet (its non-null pointers, ...); M < 2^31; the listed
+// pointers 16-byte aligned.  Then rba_begin().
+enum { RBA_GEMM_GO = -1 };
+inline int rba_gemm_prologue(int64_t M, int K, bool nonempty_ok, uintptr_t aligned) {
+  if (!(M >= 0 && K >= 32 && (K % 32) == 0)) return (int)hipErrorInvalidValue;
+  if (M == 0) return 0;
+  if (!(nonempty_ok && M < (int64_t)1 << 31 && (aligned & 15) == 0)) return (int)hipErrorInvalidValue;
+  rba_begin();
+  return RBA_GEMM_GO;
 }
+inline uintptr_t rba_or_ptrs() { return 0; }
+template <class... P>
+uintptr_t rba_or_ptrs(const void* p, P... rest) { return (uintptr_t)p | rba_or_ptrs(rest...); }
+#define RBA_GEMM_PROLOGUE(M, K, nonempty_ok, ...)                                     \
+  do {                                                                                \
+    const int go_ = rba_gemm_prologue(M, K, nonempty_ok, rba_or_ptrs(__VA_ARGS__));   \
+    if (go_ != RBA_GEMM_GO) return go_;                                               \
+  } while (0)
+// ... and the way out: the launcher's refusal, or the launch status
+inline int rba_gemm_status(int rc) { return rc ? rc : rba_launch_status(); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of the function: set it once per device (one process per GPU
 // is the deployment model, but a process that touches a second device must not inherit the first one's "already set")

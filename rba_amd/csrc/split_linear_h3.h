@@ -23,6 +23,8 @@
 // sub-stage s = 2 b + g of 32-wide block b holds, for row r, slot h ^ ((r >> 3) & 1):  k = 32 b + 16 h + 8 g + (0..7)  -- lane
 // group h = lane / 32 of the MFMA owns bytes [64 h, 64 h + 64) of its row's 128-byte block and uses them in two MFMAs (g = 0, 1).
 #pragma once
+#include <type_traits>
+
 #include "split_linear_dma.h"
 
 // tools-only knobs (exported by split_linear_dma.hip; zero in the product): see the `stagger` parameter of split_linear_h3p_kernel
@@ -106,7 +108,7 @@ __global__ void split_weight_f16x2_kernel(const float* __restrict__ w, u32x4_t* 
 // GNM (round 4): the launch also leaves the GroupNorm moments of its OUTPUT -- per (128-row tile, group of cpg consecutive output channels) the triple
 // (n, mean, M2) in the workspace layout of gn_stats_nhwc_kernel / gn_merge_kernel (group_norm.hip): ws[((b G + g) splits + s) * 3], splits = P / 128 row tiles per
 // image -- so that the statistics pass over the convolution output (134 MB at the 1/4-resolution level) is never run: rba_group_norm_nhwc_merge_f32 turns them
-// into (mean, rstd).  Every row of the tile is a valid row of ONE image (M % 128 == 0, P % 128 == 0: the launcher checks), cpg in {4, 8, 16, 32}, N % 128 == 0.
+// into (mean, rstd).  Every row of the tile is a valid row of ONE image (M % 128 == 0, P % 128 == 0: the entry point checks), cpg in {4, 8, 16, 32}, N % 128 == 0.
 // Fixed summation order: 16 rows in a lane, lane halves, the cpg lanes of a group, the four waves (deterministic).
 struct GnMoments {
   float* ws;
@@ -234,15 +236,46 @@ __device__ __forceinline__ void h3_epilogue_nchw(const f32x16_t (&accm)[CT], con
   }
 }
 
-// ACT: 0 none, 1 exact GELU, 2 ReLU.  CT: 32-column MFMA tiles per wave = tile width / 32 (BN = 32 CT; 128 must be a multiple).
-// Tile 128 x BN, four waves, wave w owns rows 32 w .. 32 w + 31 x all BN columns; two workgroups per CU (256 registers a wave).
+// ---- Kernel forms.  The three kernels below are templates over <ACT, [CT,] FORM>: ACT 0 none / 1 exact GELU / 2 ReLU, CT = 32-column MFMA tiles per wave
+// (tile width / 32), FORM = an OR of the option bits below -- every instantiation NAMES the options it sets, an option it does not name is off.  One vocabulary
+// for the three kernels; each kernel static_asserts that FORM holds only options it implements, and recovers them as constants under their own names.
+enum : unsigned {
+  H3_TIMING = 1u << 0,  // all: clock readings of the workgroup into dbg (tune library only)
+  H3_RES = 1u << 1,     // all: out = (residual + x W^T) + bias
+  H3_GNM = 1u << 2,     // h3l, h3p: the launch also leaves the GroupNorm moments of its output (see h3_epilogue)
+  H3_CONV = 1u << 3,    // h3l: A = implicit im2col of a 3 x 3 convolution over fp32 NHWC rows
+  H3_NCHW = 1u << 4,    // h3l: channel-major output
+  H3_GNF = 1u << 5,     // h3l: GroupNorm (+ ReLU) of the A rows folded into their staging
+  H3_PRE = 1u << 6,     // h3p: A = the producer's split fragment image
+  H3_FOUT = 1u << 7,    // h3p: out = the next Linear's split fragment image (operands swapped)
+  H3_CONVP = 1u << 8,   // h3p: 3 x 3 convolution over a split image (with H3_PRE)
+  H3_OCC1 = 1u << 9,    // h3p: one workgroup per CU, activations prefetched two blocks ahead (OCC = 1; every other form: OCC = 2)
+  H3_KS2 = 1u << 10,    // h3p: eight waves, the second four walk the odd k blocks (KS = 2)
+  H3_RS2 = 1u << 11,    // h3p: eight waves, 256 x 128 tile over one weight ring (RS = 2)
+  H3_PROBE_SHIFT = 16,  // bits 16 ..: the PROBE field (ablation builds of the tune library and the knobs build; results wrong)
+};
+constexpr unsigned h3_probe(int p) { return (unsigned)p << H3_PROBE_SHIFT; }
+constexpr int h3_probe_of(unsigned form) { return (int)(form >> H3_PROBE_SHIFT); }
+constexpr unsigned H3_FORMS = H3_TIMING | H3_RES, H3L_FORMS = H3_FORMS | H3_GNM | H3_CONV | H3_NCHW | H3_GNF,
+                   H3P_FORMS = H3_FORMS | H3_GNM | H3_PRE | H3_FOUT | H3_CONVP | H3_OCC1 | H3_KS2 | H3_RS2;
+constexpr bool h3_form_within(unsigned form, unsigned allowed) { return (form & ~allowed & ((1u << H3_PROBE_SHIFT) - 1)) == 0; }
+// launch geometry of a form: rows of its tile, threads of its workgroup, workgroups per CU it is compiled for
+constexpr int h3_tile_rows(unsigned form) { return (form & H3_RS2) ? 256 : 128; }
+constexpr int h3_threads(unsigned form) { return (form & (H3_KS2 | H3_RS2)) ? 512 : 256; }
+constexpr int h3_occupancy(unsigned form) { return (form & (H3_KS2 | H3_RS2 | H3_OCC1)) ? 1 : 2; }
+
+// The plain kernel.  Product: <ACT, 2> and <0, 2, H3_RES> (K > 256 with fewer than 160 tiles of 128 x 128); CT = 1 / 4, H3_TIMING and every PROBE: tune library only.
+// Tile 128 x BN (BN = 32 CT; 128 must be a multiple), four waves, wave w owns rows 32 w .. 32 w + 31 x all BN columns; two workgroups per CU (256 registers a wave).
 // PROBE (tune builds only, results wrong): bit 0 no weight loads in the loop, bit 1 no activation loads in the loop, bit 2 no epilogue,
 // bit 3 weight fragments read once, bit 4 no activation split, bit 5 no weight ds_write in the loop, bit 6 no barrier in the loop
-template <int ACT, int CT, int PROBE = 0, bool TIMING = false, bool RES = false>
+template <int ACT, int CT, unsigned FORM = 0>
 __global__ __launch_bounds__(256, 2) void split_linear_h3_kernel(const float* __restrict__ A, const u32x4_t* __restrict__ Wp,
                                                                 const float* __restrict__ bias, float* C, int M, int N,
                                                                 int K, int MT, int NT, unsigned long long* dbg = nullptr,
                                                                 const float* R = nullptr) {
+  static_assert(h3_form_within(FORM, H3_FORMS), "split_linear_h3_kernel: H3_TIMING, H3_RES, h3_probe()");
+  constexpr int PROBE = h3_probe_of(FORM);
+  constexpr bool TIMING = FORM & H3_TIMING, RES = FORM & H3_RES;
   unsigned long long tm[4];
   if (TIMING) tm[0] = wall_clock64();
   constexpr int BM = 128, BN = 32 * CT;
@@ -400,13 +433,18 @@ struct GnFold {
   const float* beta;
   int G, cpg, relu;
 };
-template <int ACT, int CT, int PROBE = 0, bool TIMING = false, bool CONV = false, bool RES = false, bool NCHW = false, bool GNF = false, bool GNM = false>
+// Product forms (CT = 4 or 2 each): <ACT>, <0, H3_RES> (K <= 256), <0, H3_CONV>, <0, H3_NCHW>, <0, H3_NCHW | H3_GNF> (split_linear_gnf.hip) and <0, 4, H3_GNM>;
+// H3_TIMING and every PROBE: tune library only.
+template <int ACT, int CT, unsigned FORM = 0>
 __global__ __launch_bounds__(256, 2) void split_linear_h3l_kernel(const float* __restrict__ A, const u32x4_t* __restrict__ Wp,
                                                                  const float* __restrict__ bias, float* C, int M, int N,
                                                                  int K, int MT, int NT, unsigned long long* dbg = nullptr,
                                                                  ConvShape cs = ConvShape{0, 0, 0}, const float* R = nullptr, int rows_per_image = 0,
                                                                  GnFold gn = GnFold{nullptr, nullptr, nullptr, 1, 1, 0},
                                                                  GnMoments gm = GnMoments{nullptr, 1, 1, 128}) {
+  static_assert(h3_form_within(FORM, H3L_FORMS), "split_linear_h3l_kernel: H3_TIMING, H3_RES, H3_GNM, H3_CONV, H3_NCHW, H3_GNF, h3_probe()");
+  constexpr int PROBE = h3_probe_of(FORM);
+  constexpr bool TIMING = FORM & H3_TIMING, CONV = FORM & H3_CONV, RES = FORM & H3_RES, NCHW = FORM & H3_NCHW, GNF = FORM & H3_GNF, GNM = FORM & H3_GNM;
   unsigned long long tm[4];
   if (TIMING) tm[0] = wall_clock64();
   constexpr int BM = 128, BN = 32 * CT;
@@ -665,21 +703,26 @@ __device__ __forceinline__ void h3_epilogue_split(const f32x16_t (&accm)[CT], co
 // copy of waves 0-3 that works on the odd 32-wide blocks of K (own weight ring in LDS, same barriers), so that every SIMD has a second
 // wave to issue from while the first waits -- what a second workgroup does for the larger launches.  After the loop the odd half's
 // accumulators are added to the even half's through LDS (two passes of 64 KiB, fixed order: deterministic) and waves 0-3 run the epilogue.
-// Instantiated by the tune library only (cfg 6004 / 6104): fc2 of Swin stage 3 62.6 -> 59.3 us, proj unchanged (26.4 us), and the halves'
-// summation order differs from the one-set kernel's -- not worth a second numerical form in the product.
+// On fp32 rows (tune library, cfg 6004): fc2 of Swin stage 3 62.6 -> 59.3 us, proj unchanged (26.4 us); the halves' summation order differs from the
+// one-set kernel's.  The product launches it on split images where h3p_use_ks2 says so (H3_PRE | H3_KS2, with or without H3_RES).
 // CONVP (with PRE, two workgroups per CU): the 3 x 3 convolution as an implicit GEMM over the producer's split image of the NHWC input
 // (rows = pixels, K = 9 Cin, k = tap * Cin + channel): the four pieces of a lane's row for block (tap, channel block) are the pieces
 // of the NEIGHBOUR pixel's row (row + dy W + dx) -- 32 lanes still read one or two contiguous runs -- zeroed where the tap leaves the image.
-// RS = 2 (round 4, tune library only -- measured in profiles/r04_k6_rs2.txt): EIGHT waves, two per SIMD, as ONE workgroup of 256 x 128: waves 4-7 are
+// RS = 2 (round 4 -- measured in profiles/r04_k6_rs2.txt; the product launches it on split images where h3p_use_rs2 says so): EIGHT waves, two per SIMD, as ONE workgroup of 256 x 128: waves 4-7 are
 // a second copy of waves 0-3 that owns the NEXT 128 rows and walks the same k blocks through the SAME weight ring (staged once by all 512 threads), so
 // the packed weight crosses the vector L1 once per 256 rows instead of once per 128: operand traffic per MFMA 42.7 -> 32 B/clk/CU at full matrix rate.
-template <int ACT, int PROBE = 0, bool TIMING = false, bool RES = false, int OCC = 2, bool PRE = false, bool FOUT = false, int KS = 1,
-          bool CONVP = false, int RS = 1, bool GNM = false>
-__global__ __launch_bounds__(256 * KS * RS, (KS == 2 || RS == 2) ? 1 : OCC) void split_linear_h3p_kernel(const float* __restrict__ A, const u32x4_t* __restrict__ Wp,
+// Product forms: on fp32 rows <ACT> and <0, H3_RES>, each also with H3_OCC1 (reached with rba_k6_occ = 1 only); on split images H3_PRE with {H3_RES or ACT} x
+// {-, H3_OCC1, H3_KS2, H3_RS2}; <1, H3_FOUT> with {-, H3_OCC1, H3_PRE, H3_PRE | H3_OCC1, H3_PRE | H3_RS2}; <0, H3_PRE | H3_CONVP> with {-, H3_RS2} x {-, H3_GNM}.
+// Tune library only: H3_TIMING, every PROBE, H3_KS2 / H3_RS2 on fp32 rows, H3_PRE | H3_OCC1 | H3_KS2.
+template <int ACT, unsigned FORM = 0>
+__global__ __launch_bounds__(h3_threads(FORM), h3_occupancy(FORM)) void split_linear_h3p_kernel(const float* __restrict__ A, const u32x4_t* __restrict__ Wp,
                                                                  const float* __restrict__ bias, float* C, int M, int N,
                                                                  int K, int MT, int NT, unsigned long long* dbg = nullptr,
                                                                  const float* R = nullptr, ConvShape cs = ConvShape{0, 0, 0}, int stagger = 0,
                                                                  GnMoments gm = GnMoments{nullptr, 1, 1, 128}) {
+  static_assert(h3_form_within(FORM, H3P_FORMS), "split_linear_h3p_kernel: H3_TIMING, H3_RES, H3_GNM, H3_PRE, H3_FOUT, H3_CONVP, H3_OCC1, H3_KS2, H3_RS2, h3_probe()");
+  constexpr int PROBE = h3_probe_of(FORM), OCC = (FORM & H3_OCC1) ? 1 : 2, KS = (FORM & H3_KS2) ? 2 : 1, RS = (FORM & H3_RS2) ? 2 : 1;
+  constexpr bool TIMING = FORM & H3_TIMING, RES = FORM & H3_RES, PRE = FORM & H3_PRE, FOUT = FORM & H3_FOUT, CONVP = FORM & H3_CONVP, GNM = FORM & H3_GNM;
   static_assert(!GNM || (KS == 1 && !FOUT), "output moments: fp32-row epilogue, one wave set per K");
   unsigned long long tm[4];
   if (TIMING) tm[0] = wall_clock64();
@@ -962,15 +1005,70 @@ __global__ __launch_bounds__(256 * KS * RS, (KS == 2 || RS == 2) ? 1 : OCC) void
   }
 }
 
-template <int ACT, int PROBE = 0, int OCC = 2, int KS = 1>
-int launch_h3p(const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, PROBE, false, false, OCC, false, false, KS>), dim3((unsigned)(MT * NT)), dim3(256 * KS), 0, stream, x,
-                     wp, bias, out, (int)M, N, K, (int)MT, NT, nullptr);
+// ---- Launching.  One argument block for the three kernels (what a form does not read keeps its default) and one launcher per kernel: tile counts from the
+// form, the grid guard, the launch.
+struct H3Args {
+  const void* x;                                           // fp32 rows, or the split fragment image (H3_PRE)
+  const u32x4_t* wp;
+  const float* bias;
+  void* out;                                               // fp32 rows, or the split fragment image (H3_FOUT)
+  int64_t M;
+  int N, K;                                                // (convolutions: K = 9 Cin)
+  hipStream_t stream;
+  const float* res = nullptr;                              // H3_RES
+  unsigned long long* dbg = nullptr;                       // H3_TIMING (and the RBA_GNF_DEBUG dump)
+  ConvShape cs = ConvShape{0, 0, 0};                       // H3_CONV, H3_CONVP
+  int rows_per_image = 0;                                  // H3_NCHW, H3_GNF
+  GnFold gn = GnFold{nullptr, nullptr, nullptr, 1, 1, 0};  // H3_GNF
+  GnMoments gm = GnMoments{nullptr, 1, 1, 128};            // H3_GNM
+  int stagger = 0;                                         // h3p, two workgroups per CU: see the kernel
+};
+
+// MT x NT tiles of rows x cols cover M x N; false where that grid does not fit a launch (2^31 workgroups or more)
+inline bool h3_grid(const H3Args& a, int rows, int cols, int& MT, int& NT) {
+  const int64_t mt = (a.M + rows - 1) / rows;
+  MT = (int)mt;
+  NT = (a.N + cols - 1) / cols;
+  return mt * NT < (int64_t)1 << 31;
+}
+
+template <int ACT, int CT, unsigned FORM = 0>
+int launch_h3(const H3Args& a) {
+  int MT, NT;
+  if (!h3_grid(a, 128, 32 * CT, MT, NT)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((split_linear_h3_kernel<ACT, CT, FORM>), dim3((unsigned)MT * NT), dim3(256), 0, a.stream, reinterpret_cast<const float*>(a.x), a.wp, a.bias,
+                     reinterpret_cast<float*>(a.out), (int)a.M, a.N, a.K, MT, NT, a.dbg, a.res);
   return 0;
 }
+
+template <int ACT, int CT, unsigned FORM = 0>
+int launch_h3l(const H3Args& a) {
+  int MT, NT;
+  if (!h3_grid(a, 128, 32 * CT, MT, NT)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((split_linear_h3l_kernel<ACT, CT, FORM>), dim3((unsigned)MT * NT), dim3(256), 0, a.stream, reinterpret_cast<const float*>(a.x), a.wp, a.bias,
+                     reinterpret_cast<float*>(a.out), (int)a.M, a.N, a.K, MT, NT, a.dbg, a.cs, a.res, a.rows_per_image, a.gn, a.gm);
+  return 0;
+}
+
+template <int ACT, unsigned FORM = 0>
+int launch_h3p(const H3Args& a) {
+  int MT, NT;
+  if (!h3_grid(a, h3_tile_rows(FORM), 128, MT, NT)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, FORM>), dim3((unsigned)MT * NT), dim3(h3_threads(FORM)), 0, a.stream, reinterpret_cast<const float*>(a.x), a.wp,
+                     a.bias, reinterpret_cast<float*>(a.out), (int)a.M, a.N, a.K, MT, NT, a.dbg, a.res, a.cs, h3_threads(FORM) == 256 ? a.stagger : 0, a.gm);
+  return 0;
+}
+
+// The run-time activation (0 none / 1 GELU / 2 ReLU) as a compile-time one: f(std::integral_constant<int, act>{})
+template <class F>
+int h3_with_act(int act, F&& f) {
+  if (act == 1) return f(std::integral_constant<int, 1>{});
+  if (act == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 0>{});
+}
+
+// ---- Shape rules
+inline int64_t tiles128(int64_t M, int N) { return ((M + 127) / 128) * ((N + 127) / 128); }
 
 // At most one workgroup per CU (<= 256 tiles): the OCC = 1 build (no second workgroup to share the register file with, so the
 // activations are prefetched two blocks ahead): -4 ... -9 % on Swin stage-3/4 proj and fc2 (profiles/r02_k6_h3p_ablation.txt).
@@ -979,18 +1077,7 @@ int launch_h3p(const float* x, const u32x4_t* wp, const float* bias, float* out,
 // prefetch -- 4-9 % faster alone, but it monopolises the CU: 128.8 -> 132.7 images/s with three streams, single stream unchanged
 // (profiles/r03_k6_occ.txt)
 RBA_KNOB_EXTERN(rba_k6_occ, 2);
-inline bool h3p_single_resident(int64_t M, int N) { return rba_k6_occ == 1 && ((M + 127) / 128) * ((N + 127) / 128) <= 256; }
-
-inline int launch_h3p_act(int act, const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, hipStream_t st) {
-  if (h3p_single_resident(M, N)) {
-    if (act == 1) return launch_h3p<1, 0, 1>(x, wp, bias, out, M, N, K, st);
-    if (act == 2) return launch_h3p<2, 0, 1>(x, wp, bias, out, M, N, K, st);
-    return launch_h3p<0, 0, 1>(x, wp, bias, out, M, N, K, st);
-  }
-  if (act == 1) return launch_h3p<1>(x, wp, bias, out, M, N, K, st);
-  if (act == 2) return launch_h3p<2>(x, wp, bias, out, M, N, K, st);
-  return launch_h3p<0>(x, wp, bias, out, M, N, K, st);
-}
+inline bool h3p_single_resident(int64_t M, int N) { return rba_k6_occ == 1 && tiles128(M, N) <= 256; }
 
 // Round 4: the 256 x 128 form (RS = 2: eight waves, one weight ring for two 128-row halves -- see the kernel) for launches whose tiles fill the
 // chip evenly.  Measured (profiles/r04_k6_rs2.txt, isolated launches, bit-identical results): 1.10-1.15x where the 256 x 128 tiles make whole
@@ -1027,204 +1114,46 @@ RBA_KNOB_EXTERN(rba_k6_ks, 0);
 inline bool h3p_use_ks2(int64_t M, int N, int K) {
   if (rba_k6_ks == 1 || (K & 63) || K < 128) return false;
   if (rba_k6_ks == 2) return true;
-  const int64_t t = ((M + 127) / 128) * ((N + 127) / 128);
+  const int64_t t = tiles128(M, N);
   return !h3p_multi_stream() && t > 128 && t <= 256 && K >= 1024;
 }
 
-// A operand = the producer's split fragment image (PRE); residual may be null
-template <int ACT, bool RES, int OCC>
-int launch_h3p_pre(const void* xf, const u32x4_t* wp, const float* bias, const float* res, float* out, int64_t M, int N, int K,
-                   hipStream_t st) {
-  const int NT = (N + 127) / 128;
-  if (OCC == 2 && h3p_use_ks2(M, N, K)) {
-    const int64_t MT1 = (M + 127) / 128;
-    if (MT1 * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, 0, false, RES, 2, true, false, 2>), dim3((unsigned)(MT1 * NT)), dim3(512), 0, st,
-                       reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, K, (int)MT1, NT, nullptr, res, ConvShape{0, 0, 0}, 0);
-    return 0;
+// The pipelined kernel's launch geometry by shape: FORM as it stands (128 x 128 tiles, two workgroups per CU) or one of its alternatives -- the single-resident
+// build, the K-split form, the 256 x 128 form, asked in that order.  ALT: the alternatives the caller's form has (only those are instantiated).
+template <int ACT, unsigned FORM, unsigned ALT>
+int launch_h3p_by_shape(const H3Args& a) {
+  static_assert((ALT & ~(H3_OCC1 | H3_KS2 | H3_RS2)) == 0 && (FORM & (H3_OCC1 | H3_KS2 | H3_RS2)) == 0, "FORM: the base form; ALT: geometry bits");
+  if constexpr ((ALT & H3_OCC1) != 0) {
+    if (h3p_single_resident(a.M, a.N)) return launch_h3p<ACT, FORM | H3_OCC1>(a);
   }
-  if (OCC == 2 && h3p_use_rs2(M, N, K)) {
-    const int64_t MT2 = (M + 255) / 256;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, 0, false, RES, 2, true, false, 1, false, 2>), dim3((unsigned)(MT2 * NT)), dim3(512), 0, st,
-                       reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, K, (int)MT2, NT, nullptr, res, ConvShape{0, 0, 0}, 0);
-    return 0;
+  if constexpr ((ALT & H3_KS2) != 0) {
+    if (h3p_use_ks2(a.M, a.N, a.K)) return launch_h3p<ACT, FORM | H3_KS2>(a);
   }
-  const int64_t MT = (M + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, 0, false, RES, OCC, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st,
-                     reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, K, (int)MT, NT, nullptr, res, ConvShape{0, 0, 0}, rba_k6_stagger);
-  return 0;
-}
-// out = the split fragment image of act(x W^T + bias) (FOUT); x either fp32 rows or a split image (PRE)
-template <int ACT, bool PRE, int OCC>
-int launch_h3p_fout(const void* x, const u32x4_t* wp, const float* bias, void* out_frag, int64_t M, int N, int K, hipStream_t st) {
-  const int NT = (N + 127) / 128;
-  if (OCC == 2 && PRE && h3p_use_rs2(M, N, K)) {
-    const int64_t MT2 = (M + 255) / 256;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, 0, false, false, 2, true, true, 1, false, 2>), dim3((unsigned)(MT2 * NT)), dim3(512), 0, st,
-                       reinterpret_cast<const float*>(x), wp, bias, reinterpret_cast<float*>(out_frag), (int)M, N, K, (int)MT2, NT, nullptr, nullptr,
-                       ConvShape{0, 0, 0}, 0);
-    return 0;
+  if constexpr ((ALT & H3_RS2) != 0) {   // (output moments are per 128-row tile: the 256-row form only where both halves are whole tiles)
+    if ((!(FORM & H3_GNM) || (a.M & 255) == 0) && h3p_use_rs2(a.M, a.N, a.K)) return launch_h3p<ACT, FORM | H3_RS2>(a);
   }
-  const int64_t MT = (M + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3p_kernel<ACT, 0, false, false, OCC, PRE, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st,
-                     reinterpret_cast<const float*>(x), wp, bias, reinterpret_cast<float*>(out_frag), (int)M, N, K, (int)MT, NT, nullptr,
-                     nullptr, ConvShape{0, 0, 0}, rba_k6_stagger);
-  return 0;
-}
-// the same convolution leaving the GroupNorm moments of its output (GNM, see h3_epilogue)
-inline int launch_h3p_conv_pre_gnm(const void* xf, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int H, int W, int Cin,
-                                   const GnMoments gm, hipStream_t st) {
-  const int NT = (N + 127) / 128;
-  if ((M & 255) == 0 && h3p_use_rs2(M, N, 9 * Cin)) {                    // moments are per 128-row tile: the 256-row form only where both halves are whole tiles
-    const int64_t MT2 = (M + 255) / 256;
-    if (MT2 * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, true, false, 1, true, 2, true>), dim3((unsigned)(MT2 * NT)), dim3(512), 0, st,
-                       reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, 9 * Cin, (int)MT2, NT, nullptr, nullptr, ConvShape{H, W, Cin}, 0, gm);
-    return 0;
-  }
-  const int64_t MT = (M + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, true, false, 1, true, 1, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st,
-                     reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, 9 * Cin, (int)MT, NT, nullptr, nullptr, ConvShape{H, W, Cin}, 0, gm);
-  return 0;
-}
-// fp32 rows in, fp32 rows out, no activation, 128-column tiles, plus the output's GroupNorm moments (the FPN's lateral 1 x 1 convolutions, K <= 256)
-inline int launch_h3l_gnm(const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, const GnMoments gm, hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<0, 4, 0, false, false, false, false, false, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, stream, x, wp, bias, out,
-                     (int)M, N, K, (int)MT, NT, nullptr, ConvShape{0, 0, 0}, nullptr, 0, GnFold{nullptr, nullptr, nullptr, 1, 1, 0}, gm);
-  return 0;
+  return launch_h3p<ACT, FORM>(a);
 }
 
-// 3 x 3 convolution (pad 1) over the split image of NHWC activations: M = B H W output pixels, K = 9 Cin (two workgroups per CU)
-inline int launch_h3p_conv_pre(const void* xf, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int H, int W, int Cin,
-                               hipStream_t st) {
-  const int NT = (N + 127) / 128;
-  if (h3p_use_rs2(M, N, 9 * Cin)) {
-    const int64_t MT2 = (M + 255) / 256;
-    if (MT2 * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, true, false, 1, true, 2>), dim3((unsigned)(MT2 * NT)), dim3(512), 0, st,
-                       reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, 9 * Cin, (int)MT2, NT, nullptr, nullptr, ConvShape{H, W, Cin});
-    return 0;
-  }
-  const int64_t MT = (M + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, true, false, 1, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st,
-                     reinterpret_cast<const float*>(xf), wp, bias, out, (int)M, N, 9 * Cin, (int)MT, NT, nullptr, nullptr, ConvShape{H, W, Cin});
-  return 0;
-}
-template <int OCC>
-int launch_h3p_pre_act(int act, const void* xf, const u32x4_t* wp, const float* bias, const float* res, float* out, int64_t M, int N,
-                       int K, hipStream_t st) {
-  if (res) return launch_h3p_pre<0, true, OCC>(xf, wp, bias, res, out, M, N, K, st);
-  if (act == 1) return launch_h3p_pre<1, false, OCC>(xf, wp, bias, nullptr, out, M, N, K, st);
-  if (act == 2) return launch_h3p_pre<2, false, OCC>(xf, wp, bias, nullptr, out, M, N, K, st);
-  return launch_h3p_pre<0, false, OCC>(xf, wp, bias, nullptr, out, M, N, K, st);
+// fp32 rows in, fp32 rows out (FORM: 0 or H3_RES).  K <= 256 (Swin stages 1-2: many short tiles) runs the LDS-staged form, longer K the straight-to-register
+// forms (software-pipelined with 128-column tiles, plain with 64-column tiles); 128 x 64 tiles when there are fewer than 160 tiles of 128 x 128.  Chosen in
+// the whole model (bench.py, one stream: 89.1 images/s; with the LDS-staged form up to K = 1024, which the isolated sweep of profiles/r02_k6_f16x3.txt
+// prefers by 2-4 %, 85.8).
+// wide: 128-column tiles from 160 tiles up (sweeps: 116-128 tiles prefer 64, 168-192 prefer 128)
+inline bool h3_wide(int64_t M, int N) { return tiles128(M, N) >= 160 || N <= 64; }
+template <int ACT, unsigned FORM>
+int launch_h3_rows(const H3Args& a) {
+  const bool wide = h3_wide(a.M, a.N);
+  if (a.K <= 256) return wide ? launch_h3l<ACT, 4, FORM>(a) : launch_h3l<ACT, 2, FORM>(a);
+  return wide ? launch_h3p_by_shape<ACT, FORM, H3_OCC1>(a) : launch_h3<ACT, 2, FORM>(a);
 }
 
-template <int ACT, int CT, int PROBE = 0>
-int launch_h3l(const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<ACT, CT, PROBE>), dim3((unsigned)(MT * NT)), dim3(256), 0, stream, x, wp, bias, out, (int)M, N,
-                     K, (int)MT, NT, nullptr);
-  return 0;
-}
-
-// 3 x 3 convolution (pad 1) over NHWC activations as an implicit GEMM: M = B H W output pixels, K = 9 Cin
-template <int CT>
-int launch_h3l_conv(const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int H, int W, int Cin,
-                    hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<0, CT, 0, false, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, stream, x, wp, bias, out,
-                     (int)M, N, 9 * Cin, (int)MT, NT, nullptr, ConvShape{H, W, Cin});
-  return 0;
-}
-
-// x [B P, K] fp32 rows -> out [B, N, P] (no activation): the LDS-staged kernel with the channel-major epilogue
-template <int CT>
-int launch_h3l_nchw(const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, int P, hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<0, CT, 0, false, false, false, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, stream, x, wp, bias, out,
-                     (int)M, N, K, (int)MT, NT, nullptr, ConvShape{0, 0, 0}, nullptr, P);
-  return 0;
-}
-
-// the same with the GroupNorm (+ ReLU) of the input rows folded into the A load (GNF)
-template <int CT>
-int launch_h3l_nchw_gn(const float* x, const GnFold gn, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, int P, hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<0, CT, 0, false, false, false, true, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, stream, x, wp, bias, out,
-                     (int)M, N, K, (int)MT, NT, nullptr, ConvShape{0, 0, 0}, nullptr, P, gn);
-  return 0;
-}
-
-template <int CT>
-int launch_h3l_act(int act, const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, hipStream_t st) {
-  if (act == 1) return launch_h3l<1, CT>(x, wp, bias, out, M, N, K, st);
-  if (act == 2) return launch_h3l<2, CT>(x, wp, bias, out, M, N, K, st);
-  return launch_h3l<0, CT>(x, wp, bias, out, M, N, K, st);
-}
-
-template <int ACT, int CT, int PROBE = 0>
-int launch_h3(const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, hipStream_t stream) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3_kernel<ACT, CT, PROBE>), dim3((unsigned)(MT * NT)), dim3(256), 0, stream, x, wp, bias, out, (int)M, N,
-                     K, (int)MT, NT);
-  return 0;
-}
-
-template <int CT>
-int launch_h3_act(int act, const float* x, const u32x4_t* wp, const float* bias, float* out, int64_t M, int N, int K, hipStream_t st) {
-  if (act == 1) return launch_h3<1, CT>(x, wp, bias, out, M, N, K, st);
-  if (act == 2) return launch_h3<2, CT>(x, wp, bias, out, M, N, K, st);
-  return launch_h3<0, CT>(x, wp, bias, out, M, N, K, st);
-}
-
-// out = (residual + x W^T) + bias  (no activation): the residual forms of the three kernels
-template <int CT>
-int launch_h3_res(const float* x, const u32x4_t* wp, const float* bias, const float* res, float* out, int64_t M, int N, int K, hipStream_t st) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3_kernel<0, CT, 0, false, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out, (int)M, N, K,
-                     (int)MT, NT, nullptr, res);
-  return 0;
-}
-template <int CT>
-int launch_h3l_res(const float* x, const u32x4_t* wp, const float* bias, const float* res, float* out, int64_t M, int N, int K, hipStream_t st) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 32 * CT - 1) / (32 * CT);
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<0, CT, 0, false, false, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out, (int)M,
-                     N, K, (int)MT, NT, nullptr, ConvShape{0, 0, 0}, res);
-  return 0;
-}
-inline int launch_h3p_res(const float* x, const u32x4_t* wp, const float* bias, const float* res, float* out, int64_t M, int N, int K,
-                          hipStream_t st) {
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 127) / 128;
-  if (MT * NT >= (int64_t)1 << 31) return (int)hipErrorInvalidValue;
-  if (rba_k6_occ == 1 && MT * NT <= 256)
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, true, 1>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out, (int)M,
-                       N, K, (int)MT, NT, nullptr, res);
-  else
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out, (int)M, N,
-                       K, (int)MT, NT, nullptr, res);
-  return 0;
+// NEVER CALLED.  Five launch helpers used to stand here as non-template inline functions, so EVERY translation unit that includes this header -- split_linear_gnf.hip
+// and the tune probes too, which launch none of them -- has always compiled their thirteen kernels.  Naming the thirteen here keeps each unit's device code what
+// it was, kernel for kernel (tools/kernel_code_diff.py); taking them out of the units that do not launch them is a change of its own, with its own check.
+inline int h3_forms_compiled_in_every_unit(const H3Args& a) {
+  return h3_with_act(0, [&](auto ACT) { return launch_h3p_by_shape<ACT, 0, H3_OCC1>(a); }) | launch_h3p_by_shape<0, H3_RES, H3_OCC1>(a) |
+         launch_h3p_by_shape<0, H3_PRE | H3_CONVP, H3_RS2>(a) | launch_h3p_by_shape<0, H3_PRE | H3_CONVP | H3_GNM, H3_RS2>(a) | launch_h3l<0, 4, H3_GNM>(a);
 }
 
 #endif  // RBA_H3_HELPERS_ONLY

@@ -7,10 +7,10 @@
 
 extern "C" int rba_gnf_probe_form1_dbg0_unpacked(const float* x, const float* mr, const float* gamma, const float* beta, int G, int relu, const void* weight_packed,
                                        const float* bias, float* out, int64_t M, int N, int K, int rows_per_image, unsigned long long* dbg, void* stream) {
-  const GnFold gn{mr, gamma, beta, G, K / G, relu ? 1 : 0};
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 127) / 128;
-  hipLaunchKernelGGL((split_linear_h3l_kernel<0, 4, 0, false, false, false, true, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x,
-                     reinterpret_cast<const u32x4_t*>(weight_packed), bias, out, (int)M, N, K, (int)MT, NT, dbg, ConvShape{0, 0, 0}, nullptr, rows_per_image, gn);
-  return (int)hipGetLastError();
+  H3Args a{x, reinterpret_cast<const u32x4_t*>(weight_packed), bias, out, M, N, K, (hipStream_t)stream};
+  a.dbg = dbg;
+  a.rows_per_image = rows_per_image;
+  a.gn = GnFold{mr, gamma, beta, G, K / G, relu ? 1 : 0};
+  const int rc = launch_h3l<0, 4, H3_NCHW | H3_GNF>(a);
+  return rc ? rc : (int)hipGetLastError();
 }

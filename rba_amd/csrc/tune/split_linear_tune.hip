@@ -128,92 +128,56 @@ extern "C" int rba_split_linear_h3_tune(const float* x, const void* weight_packe
                                         int act, int cfg, void* stream) {
   RBA_CHECK_ARG(M >= 1 && N >= 1 && K >= 32 && (K % 32) == 0 && act >= 0 && act <= 2);
   rba_begin();
-  const u32x4_t* wp = reinterpret_cast<const u32x4_t*>(weight_packed);
-  hipStream_t st = (hipStream_t)stream;
+  const H3Args a{x, reinterpret_cast<const u32x4_t*>(weight_packed), bias, out, M, N, K, (hipStream_t)stream};
   int rc;
   switch (cfg) {
-    case 4: rc = launch_h3_act<4>(act, x, wp, bias, out, M, N, K, st); break;
-    case 1004: rc = launch_h3l_act<4>(act, x, wp, bias, out, M, N, K, st); break;
-    case 1002: rc = launch_h3l_act<2>(act, x, wp, bias, out, M, N, K, st); break;
-    case 1014: rc = launch_h3l<1, 4, 1>(x, wp, bias, out, M, N, K, st); break;
-    case 1044: rc = launch_h3l<1, 4, 4>(x, wp, bias, out, M, N, K, st); break;
-    case 1054: rc = launch_h3l<1, 4, 5>(x, wp, bias, out, M, N, K, st); break;
-    case 1164: rc = launch_h3l<1, 4, 16>(x, wp, bias, out, M, N, K, st); break;
-    case 1324: rc = launch_h3l<1, 4, 32>(x, wp, bias, out, M, N, K, st); break;
-    case 1644: rc = launch_h3l<1, 4, 64>(x, wp, bias, out, M, N, K, st); break;
-    case 2284: rc = launch_h3l<1, 4, 128>(x, wp, bias, out, M, N, K, st); break;
-    case 4004: rc = launch_h3p_act(act, x, wp, bias, out, M, N, K, st); break;
-    case 5004:
-      rc = act == 1 ? launch_h3p<1, 0, 1>(x, wp, bias, out, M, N, K, st) : act == 2 ? launch_h3p<2, 0, 1>(x, wp, bias, out, M, N, K, st)
-                                                                                      : launch_h3p<0, 0, 1>(x, wp, bias, out, M, N, K, st);
-      break;
-    case 6004:
-      rc = act == 1 ? launch_h3p<1, 0, 1, 2>(x, wp, bias, out, M, N, K, st) : act == 2 ? launch_h3p<2, 0, 1, 2>(x, wp, bias, out, M, N, K, st)
-                                                                                         : launch_h3p<0, 0, 1, 2>(x, wp, bias, out, M, N, K, st);
-      break;
-    case 6104: {                                                                     // timing only: x read as if it were a split image
-      const int64_t MT = (M + 127) / 128; const int NT = (N + 127) / 128;
-      hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 1, true, false, 2>), dim3((unsigned)(MT * NT)), dim3(512), 0, st, x, wp, bias, out,
-                         (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
+    case 4: rc = h3_with_act(act, [&](auto ACT) { return launch_h3<ACT, 4>(a); }); break;
+    case 1004: rc = h3_with_act(act, [&](auto ACT) { return launch_h3l<ACT, 4>(a); }); break;
+    case 1002: rc = h3_with_act(act, [&](auto ACT) { return launch_h3l<ACT, 2>(a); }); break;
+    case 1014: rc = launch_h3l<1, 4, h3_probe(1)>(a); break;
+    case 1044: rc = launch_h3l<1, 4, h3_probe(4)>(a); break;
+    case 1054: rc = launch_h3l<1, 4, h3_probe(5)>(a); break;
+    case 1164: rc = launch_h3l<1, 4, h3_probe(16)>(a); break;
+    case 1324: rc = launch_h3l<1, 4, h3_probe(32)>(a); break;
+    case 1644: rc = launch_h3l<1, 4, h3_probe(64)>(a); break;
+    case 2284: rc = launch_h3l<1, 4, h3_probe(128)>(a); break;
+    case 4004: rc = h3_with_act(act, [&](auto ACT) { return launch_h3p_by_shape<ACT, 0, H3_OCC1>(a); }); break;
+    case 5004: rc = h3_with_act(act, [&](auto ACT) { return launch_h3p<ACT, H3_OCC1>(a); }); break;
+    case 6004: rc = h3_with_act(act, [&](auto ACT) { return launch_h3p<ACT, H3_OCC1 | H3_KS2>(a); }); break;
+    case 6104: rc = launch_h3p<0, H3_PRE | H3_OCC1 | H3_KS2>(a); break;              // timing only: x read as if it were a split image
     // round 4: the product's launch forms on split-image operands (timing only: x is read as if it were a split image), one 128 x 128 tile per
     // workgroup, two workgroups per CU (5204: fp32 rows out = qkv; 5214: GELU + split image out = fc1) -- and the 256 x 128 / 8-wave / shared weight
     // ring form RS = 2 of the same two launches (7104, 7114)
-    case 5204: {
-      const int64_t MT = (M + 127) / 128; const int NT = (N + 127) / 128;
-      hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, true, false, 1>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out,
-                         (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
-    case 5214: {
-      const int64_t MT = (M + 127) / 128; const int NT = (N + 127) / 128;
-      hipLaunchKernelGGL((split_linear_h3p_kernel<1, 0, false, false, 2, true, true, 1>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out,
-                         (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
-    case 7104: {
-      const int64_t MT = (M + 255) / 256; const int NT = (N + 127) / 128;
-      hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, true, false, 1, false, 2>), dim3((unsigned)(MT * NT)), dim3(512), 0, st, x, wp, bias,
-                         out, (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
-    case 7114: {
-      const int64_t MT = (M + 255) / 256; const int NT = (N + 127) / 128;
-      hipLaunchKernelGGL((split_linear_h3p_kernel<1, 0, false, false, 2, true, true, 1, false, 2>), dim3((unsigned)(MT * NT)), dim3(512), 0, st, x, wp, bias,
-                         out, (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
-    case 7004: {                                                                     // RS = 2 on fp32 rows (results checked by tools/gemm_h3_sweep.py)
-      const int64_t MT = (M + 255) / 256; const int NT = (N + 127) / 128;
-      if (act == 1) hipLaunchKernelGGL((split_linear_h3p_kernel<1, 0, false, false, 2, false, false, 1, false, 2>), dim3((unsigned)(MT * NT)), dim3(512), 0, st, x, wp, bias, out, (int)M, N, K, (int)MT, NT, nullptr);
-      else hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 2, false, false, 1, false, 2>), dim3((unsigned)(MT * NT)), dim3(512), 0, st, x, wp, bias, out, (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
-    case 5104: {
-      const int64_t MT = (M + 127) / 128; const int NT = (N + 127) / 128;
-      hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, false, false, 1, true, false, 1>), dim3((unsigned)(MT * NT)), dim3(256), 0, st, x, wp, bias, out,
-                         (int)M, N, K, (int)MT, NT, nullptr);
-      rc = 0; break; }
-    case 4044: rc = launch_h3p<1, 4>(x, wp, bias, out, M, N, K, st); break;
-    case 4014: rc = launch_h3p<1, 1>(x, wp, bias, out, M, N, K, st); break;
-    case 4024: rc = launch_h3p<1, 2>(x, wp, bias, out, M, N, K, st); break;
-    case 4034: rc = launch_h3p<1, 3>(x, wp, bias, out, M, N, K, st); break;
-    case 4644: rc = launch_h3p<1, 64>(x, wp, bias, out, M, N, K, st); break;
-    case 4674: rc = launch_h3p<1, 67>(x, wp, bias, out, M, N, K, st); break;
-    case 2: rc = launch_h3_act<2>(act, x, wp, bias, out, M, N, K, st); break;
-    case 1: rc = launch_h3_act<1>(act, x, wp, bias, out, M, N, K, st); break;
-    case 14: rc = launch_h3<1, 4, 1>(x, wp, bias, out, M, N, K, st); break;
-    case 24: rc = launch_h3<1, 4, 2>(x, wp, bias, out, M, N, K, st); break;
-    case 34: rc = launch_h3<1, 4, 3>(x, wp, bias, out, M, N, K, st); break;
-    case 44: rc = launch_h3<1, 4, 4>(x, wp, bias, out, M, N, K, st); break;
-    case 74: rc = launch_h3<1, 4, 7>(x, wp, bias, out, M, N, K, st); break;
-    case 154: rc = launch_h3<1, 4, 15>(x, wp, bias, out, M, N, K, st); break;
-    case 234: rc = launch_h3<1, 4, 23>(x, wp, bias, out, M, N, K, st); break;
-    case 394: rc = launch_h3<1, 4, 39>(x, wp, bias, out, M, N, K, st); break;
-    case 634: rc = launch_h3<1, 4, 63>(x, wp, bias, out, M, N, K, st); break;
-    case 1274: rc = launch_h3<1, 4, 127>(x, wp, bias, out, M, N, K, st); break;
-    case 84: rc = launch_h3<1, 4, 8>(x, wp, bias, out, M, N, K, st); break;
-    case 164: rc = launch_h3<1, 4, 16>(x, wp, bias, out, M, N, K, st); break;
-    case 644: rc = launch_h3<1, 4, 64>(x, wp, bias, out, M, N, K, st); break;
+    case 5204: rc = launch_h3p<0, H3_PRE>(a); break;
+    case 5214: rc = launch_h3p<1, H3_PRE | H3_FOUT>(a); break;
+    case 7104: rc = launch_h3p<0, H3_PRE | H3_RS2>(a); break;
+    case 7114: rc = launch_h3p<1, H3_PRE | H3_FOUT | H3_RS2>(a); break;
+    case 7004: rc = act == 1 ? launch_h3p<1, H3_RS2>(a) : launch_h3p<0, H3_RS2>(a); break;   // RS = 2 on fp32 rows (results checked by tools/gemm_h3_sweep.py)
+    case 5104: rc = launch_h3p<0, H3_PRE | H3_OCC1>(a); break;
+    case 4044: rc = launch_h3p<1, h3_probe(4)>(a); break;
+    case 4014: rc = launch_h3p<1, h3_probe(1)>(a); break;
+    case 4024: rc = launch_h3p<1, h3_probe(2)>(a); break;
+    case 4034: rc = launch_h3p<1, h3_probe(3)>(a); break;
+    case 4644: rc = launch_h3p<1, h3_probe(64)>(a); break;
+    case 4674: rc = launch_h3p<1, h3_probe(67)>(a); break;
+    case 2: rc = h3_with_act(act, [&](auto ACT) { return launch_h3<ACT, 2>(a); }); break;
+    case 1: rc = h3_with_act(act, [&](auto ACT) { return launch_h3<ACT, 1>(a); }); break;
+    case 14: rc = launch_h3<1, 4, h3_probe(1)>(a); break;
+    case 24: rc = launch_h3<1, 4, h3_probe(2)>(a); break;
+    case 34: rc = launch_h3<1, 4, h3_probe(3)>(a); break;
+    case 44: rc = launch_h3<1, 4, h3_probe(4)>(a); break;
+    case 74: rc = launch_h3<1, 4, h3_probe(7)>(a); break;
+    case 154: rc = launch_h3<1, 4, h3_probe(15)>(a); break;
+    case 234: rc = launch_h3<1, 4, h3_probe(23)>(a); break;
+    case 394: rc = launch_h3<1, 4, h3_probe(39)>(a); break;
+    case 634: rc = launch_h3<1, 4, h3_probe(63)>(a); break;
+    case 1274: rc = launch_h3<1, 4, h3_probe(127)>(a); break;
+    case 84: rc = launch_h3<1, 4, h3_probe(8)>(a); break;
+    case 164: rc = launch_h3<1, 4, h3_probe(16)>(a); break;
+    case 644: rc = launch_h3<1, 4, h3_probe(64)>(a); break;
     default: return (int)hipErrorInvalidValue;
   }
-  if (rc) return rc;
-  return rba_launch_status();
+  return rba_gemm_status(rc);
 }
 
 // Timing build of the f16x3 kernel: dbg[6 wg + {0..3}] = s_memrealtime (100 MHz) at entry / loop start / loop end / exit,
@@ -221,50 +185,25 @@ extern "C" int rba_split_linear_h3_tune(const float* x, const void* weight_packe
 extern "C" int rba_split_linear_h3_timing(const float* x, const void* weight_packed, const float* bias, float* out, int64_t M, int N, int K,
                                           int probe, unsigned long long* dbg, void* stream) {
   rba_begin();
-  const u32x4_t* wp = reinterpret_cast<const u32x4_t*>(weight_packed);
-  const int64_t MT = (M + 127) / 128;
-  const int NT = (N + 127) / 128;
-  if (probe == 0)
-    hipLaunchKernelGGL((split_linear_h3_kernel<1, 4, 0, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp, bias, out,
-                       (int)M, N, K, (int)MT, NT, dbg);
-  else if (probe == 1000)
-    hipLaunchKernelGGL((split_linear_h3p_kernel<1, 0, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp, bias, out,
-                       (int)M, N, K, (int)MT, NT, dbg);
-#define RBA_H3P_T(P)                                                                                                                  \
-  else if (probe == 1100 + P) hipLaunchKernelGGL((split_linear_h3p_kernel<0, P, true>), dim3((unsigned)(MT * NT)), dim3(256), 0,       \
-                                                 (hipStream_t)stream, x, wp, bias, out, (int)M, N, K, (int)MT, NT, dbg);
+  H3Args a{x, reinterpret_cast<const u32x4_t*>(weight_packed), bias, out, M, N, K, (hipStream_t)stream};
+  a.dbg = dbg;
+  int rc;
+  if (probe == 0) rc = launch_h3<1, 4, H3_TIMING>(a);
+  else if (probe == 1000) rc = launch_h3p<1, H3_TIMING>(a);
+#define RBA_H3P_T(P) else if (probe == 1100 + P) rc = launch_h3p<0, H3_TIMING | h3_probe(P)>(a);
   RBA_H3P_T(0) RBA_H3P_T(1) RBA_H3P_T(2) RBA_H3P_T(3) RBA_H3P_T(64) RBA_H3P_T(67) RBA_H3P_T(2048) RBA_H3P_T(2560)
 #undef RBA_H3P_T
-#define RBA_H3P_T(P)                                                                                                                  \
-  else if (probe == 1200 + P) hipLaunchKernelGGL((split_linear_h3p_kernel<0, P, true, false, 1>), dim3((unsigned)(MT * NT)), dim3(256), 0, \
-                                                 (hipStream_t)stream, x, wp, bias, out, (int)M, N, K, (int)MT, NT, dbg);
+#define RBA_H3P_T(P) else if (probe == 1200 + P) rc = launch_h3p<0, H3_TIMING | H3_OCC1 | h3_probe(P)>(a);
   RBA_H3P_T(0) RBA_H3P_T(3) RBA_H3P_T(67) RBA_H3P_T(323) RBA_H3P_T(579) RBA_H3P_T(1091) RBA_H3P_T(1859) RBA_H3P_T(2048) RBA_H3P_T(2560) RBA_H3P_T(1) RBA_H3P_T(2) RBA_H3P_T(64) RBA_H3P_T(1795) RBA_H3P_T(768) RBA_H3P_T(512) RBA_H3P_T(256)
 #undef RBA_H3P_T
-  else if (probe == 1300)
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, true, false, 2, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp, bias,
-                       out, (int)M, N, K, (int)MT, NT, dbg);
-  else if (probe == 1400)
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, true, false, 1, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp, bias,
-                       out, (int)M, N, K, (int)MT, NT, dbg);
-  else if (probe == 1500)                      // round 4: the fc1 launch form (GELU, split image in and out), 128 x 128 tiles
-    hipLaunchKernelGGL((split_linear_h3p_kernel<1, 0, true, false, 2, true, true, 1>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp,
-                       bias, out, (int)M, N, K, (int)MT, NT, dbg);
-  else if (probe == 1600) {                    // ... and its 256 x 128 / 8-wave form (RS = 2)
-    const int64_t MT2 = (M + 255) / 256;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<1, 0, true, false, 2, true, true, 1, false, 2>), dim3((unsigned)(MT2 * NT)), dim3(512), 0, (hipStream_t)stream,
-                       x, wp, bias, out, (int)M, N, K, (int)MT2, NT, dbg);
-  } else if (probe == 1700) {                  // RS = 2, fp32 rows out, no activation (the qkv launch form)
-    const int64_t MT2 = (M + 255) / 256;
-    hipLaunchKernelGGL((split_linear_h3p_kernel<0, 0, true, false, 2, true, false, 1, false, 2>), dim3((unsigned)(MT2 * NT)), dim3(512), 0, (hipStream_t)stream,
-                       x, wp, bias, out, (int)M, N, K, (int)MT2, NT, dbg);
-  }
-  else if (probe == 1001)
-    hipLaunchKernelGGL((split_linear_h3l_kernel<1, 4, 0, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp, bias, out,
-                       (int)M, N, K, (int)MT, NT, dbg, ConvShape{0, 0, 0});
-  else
-    hipLaunchKernelGGL((split_linear_h3_kernel<1, 4, 127, true>), dim3((unsigned)(MT * NT)), dim3(256), 0, (hipStream_t)stream, x, wp, bias,
-                       out, (int)M, N, K, (int)MT, NT, dbg);
-  return rba_launch_status();
+  else if (probe == 1300) rc = launch_h3p<0, H3_TIMING | H3_PRE>(a);
+  else if (probe == 1400) rc = launch_h3p<0, H3_TIMING | H3_PRE | H3_OCC1>(a);
+  else if (probe == 1500) rc = launch_h3p<1, H3_TIMING | H3_PRE | H3_FOUT>(a);            // round 4: the fc1 launch form (GELU, split image in and out), 128 x 128 tiles
+  else if (probe == 1600) rc = launch_h3p<1, H3_TIMING | H3_PRE | H3_FOUT | H3_RS2>(a);   // ... and its 256 x 128 / 8-wave form (RS = 2)
+  else if (probe == 1700) rc = launch_h3p<0, H3_TIMING | H3_PRE | H3_RS2>(a);             // RS = 2, fp32 rows out, no activation (the qkv launch form)
+  else if (probe == 1001) rc = launch_h3l<1, 4, H3_TIMING>(a);
+  else rc = launch_h3<1, 4, H3_TIMING | h3_probe(127)>(a);
+  return rba_gemm_status(rc);
 }
 
 // ablations of the fused Swin MLP (mlp_fused_h3.h PROBE bits); timing only

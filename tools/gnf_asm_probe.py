@@ -15,7 +15,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "tools", "micro", "bin", "gnfasm")           # git-ignored (*.co), but it travels to the GPU box
-KERNEL = "_ZN12_GLOBAL__N_123split_linear_h3l_kernelILi0ELi4ELi0ELb0ELb0ELb0ELb1ELb1ELb0EEEvPKfPKDv4_jS2_PfiiiiiPyNS_9ConvShapeES2_iNS_6GnFoldENS_9GnMomentsE"
+KERNEL = "_ZN12_GLOBAL__N_123split_linear_h3l_kernelILi0ELi4ELj48EEEvPKfPKDv4_jS2_PfiiiiiPyNS_9ConvShapeES2_iNS_6GnFoldENS_9GnMomentsE"
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 PK1 = "\tv_pk_mul_f32 v[166:167], v[130:131], v[182:183] op_sel:[0,1]\n"
