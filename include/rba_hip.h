@@ -21,6 +21,7 @@
  *                                   ops/src/cuda/ms_deform_attn_cuda.cu:88-158)
  *   rba_reduce_f32              <- MaskFormer.semantic_inference (mask2former/maskformer_model.py:381-386)
  *                                  + get_RbA (evaluate_ood.py:143-150) + argmax (support.py:385-388)
+ *   rba_reduce_bwd_f32          <- autograd's backward of SetCriterion.outlier_loss's score (mask2former/modeling/criterion.py:449-463)
  *   rba_reduce_up4_f32          <- the same preceded by the x4 mask upsample (maskformer_model.py:294-299)
  *                                  and followed by the sem_seg_postprocess crop (maskformer_model.py:330-332)
  *   rba_resample_bilinear_f32   <- F.interpolate(mode="bilinear", align_corners=False) call sites
@@ -85,6 +86,23 @@ int rba_reduce_ws_f32(const float* mask, const float* cls_prob, float* rba, floa
  * columns < crop_w of it: rba [crop_h,crop_w], sem_seg [K,crop_h,crop_w] or NULL, argmax or NULL. */
 int rba_reduce_up4_f32(const float* mask_lowres, const float* cls_prob, float* rba, float* sem_seg,
                        int32_t* argmax, int Q, int K, int h, int w, int crop_h, int crop_w, int score_mode, void* stream);
+
+/* K1 backward.  Gradients of rba_reduce_f32's score with respect to mask and cls_prob, given grad_score [HW] = dL/d rba (the heavy differentiable
+ * piece of SetCriterion.outlier_loss, mask2former/modeling/criterion.py:449-463: sigmoid, einsum("bqc,bqhw->bchw"), tanh / logsumexp / sum):
+ *   sig = sigmoid(mask);  s[k,p] = sum_q cls_prob[q,k] sig[q,p]          (recomputed: nothing but the forward's two inputs is needed)
+ *   u[k,p] = grad_score[p] * ( -(1 - tanh^2 s) | -softmax_k(s) | -1 )    (score_mode 0 | 1 | 2; the softmax is max-subtracted)
+ *   grad_mask[q,p] = sig (1 - sig) sum_k cls_prob[q,k] u[k,p]            (sig (1 - sig) from sig: exactly 0 where sig is 0 or 1, never NaN)
+ *   grad_prob[q,k] = sum_p sig[q,p] u[k,p]
+ * grad_mask [Q,HW] and grad_prob [Q,K] are each optional (NULL = not computed), at least one is required.  Both are written element by element
+ * with plain stores, whatever they held before, and are bitwise reproducible from launch to launch: grad_prob is summed per 128-pixel tile into
+ * `workspace` and then over the tiles in a fixed order (no float atomics).  `workspace`: device memory owned by the caller, 4-byte aligned, at
+ * least rba_reduce_bwd_workspace_f32's byte count, needed only with grad_prob; its contents on entry do not matter.  1 <= K <= 160, Q >= 1,
+ * HW >= 1; anything else returns hipErrorInvalidValue without a launch. */
+int rba_reduce_bwd_workspace_f32(int Q, int K, int64_t HW, int64_t* bytes);
+int rba_reduce_bwd_f32(const float* mask, const float* cls_prob, const float* grad_score,
+                       float* grad_mask /* [Q,HW] or NULL */, float* grad_prob /* [Q,K] or NULL */,
+                       int Q, int K, int64_t HW, int score_mode,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Bilinear resample, align_corners=False, no antialias (ATen upsample_bilinear2d semantics):
  * in [C,h,w] -> out [C,H,W];  if `add` != NULL (same shape as out): out = resample(in) + add. */

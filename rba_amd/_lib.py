@@ -24,6 +24,8 @@ SIGNATURES = {
     "rba_reduce_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp],
     "rba_reduce_ws_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp],
     "rba_reduce_up4_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "rba_reduce_bwd_workspace_f32": [_i, _i, _i64, _vp],
+    "rba_reduce_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i64, _vp],
     "rba_resample_bilinear_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_ms_deform_attn_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_ms_deform_attn_fwd_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],

@@ -136,6 +136,52 @@ def rba_reduce_up4(mask_lowres, cls_prob, crop_hw, want_sem_seg=False, want_argm
     return rba, sem, arg
 
 
+_K1_BWD_WORKSPACES = {}
+
+
+def _k1_bwd_workspace(device, nbytes):
+    """K1 backward's per-tile grad_prob partial sums: one buffer per (device, stream), replaced by a larger one when a call needs more (a run
+    over varying mask sizes keeps the largest, not one per size); the kernel writes every word it later reads.  Launches that share a
+    buffer are ordered by their stream, and torch's allocator keeps a replaced buffer's memory on that stream."""
+    key = (device.index, _stream())                      # called under _hip_op: the current device IS `device`
+    ws = _K1_BWD_WORKSPACES.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _K1_BWD_WORKSPACES[key] = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device)
+    return ws
+
+
+@_hip_op
+def rba_reduce_backward(mask_pred, cls_prob, grad_score, score="rba", need_mask=True, need_prob=True):
+    """K1 backward.  mask_pred [Q,h,w], cls_prob [Q,K] (rba_reduce's inputs), grad_score [h,w] = dL/d score ->
+    (grad_mask [Q,h,w] | None, grad_prob [Q,K] | None), the gradients of rba_reduce's score (criterion.py:449-463 under autograd).
+    Both are bitwise reproducible from launch to launch."""
+    lib = _lib.load()
+    _chk(mask_pred, "mask_pred", dim=3)
+    _chk(cls_prob, "cls_prob", dim=2)
+    _chk(grad_score, "grad_score", dim=2)
+    mode = _mode(score)
+    Q, H, W = mask_pred.shape
+    if cls_prob.shape[0] != Q:
+        raise RbaHipError(f"cls_prob has {cls_prob.shape[0]} queries, mask_pred {Q}")
+    if tuple(grad_score.shape) != (H, W):
+        raise RbaHipError(f"grad_score must have shape {(H, W)}, got {tuple(grad_score.shape)}")
+    if not (need_mask or need_prob):
+        raise RbaHipError("rba_reduce_backward: at least one of need_mask / need_prob")
+    K = cls_prob.shape[1]
+    dev = mask_pred.device
+    ws, ws_bytes = None, 0
+    if need_prob:
+        n = ctypes.c_int64(0)
+        _lib.check(lib.rba_reduce_bwd_workspace_f32(Q, K, H * W, ctypes.addressof(n)), "rba_reduce_bwd_workspace_f32")
+        ws_bytes = int(n.value)
+        ws = _k1_bwd_workspace(dev, ws_bytes)
+    grad_mask = torch.empty((Q, H, W), dtype=torch.float32, device=dev) if need_mask else None
+    grad_prob = torch.empty((Q, K), dtype=torch.float32, device=dev) if need_prob else None
+    _lib.check(lib.rba_reduce_bwd_f32(_p(mask_pred), _p(cls_prob), _p(grad_score), _p(grad_mask), _p(grad_prob), Q, K, H * W, mode,
+                                      _p(ws), ws_bytes, _stream()), "rba_reduce_bwd_f32")
+    return grad_mask, grad_prob
+
+
 @_hip_op
 def resample_bilinear(x, size, add=None):
     """F.interpolate(x, size, mode="bilinear", align_corners=False) for x [C,h,w] or [B,C,h,w]; optional fused
