@@ -21,6 +21,39 @@ typedef uint32_t rba_u32x4 __attribute__((ext_vector_type(4)));
 static inline void rba_begin() { (void)hipGetLastError(); }
 static inline int rba_launch_status() { return (int)hipGetLastError(); }
 
+// The persistent-grid rule: at most `cap` workgroups, each with the same number of tiles (the last may get fewer).  All `tiles` when they fit,
+// else rounds = ceil(tiles / cap) tiles per workgroup and ceil(tiles / rounds) workgroups.
+constexpr int64_t rba_even_grid(int64_t tiles, int64_t cap) {
+  if (tiles <= cap) return tiles;
+  const int64_t rounds = (tiles + cap - 1) / cap;
+  return (tiles + rounds - 1) / rounds;
+}
+constexpr bool rba_even_grid_covers(int64_t max_tiles, int64_t cap) {   // grid <= cap and ceil(tiles / cap) rounds of it reach every tile
+  for (int64_t t = 0; t <= max_tiles; ++t) {
+    const int64_t g = rba_even_grid(t, cap);
+    if (g > cap || g * ((t + cap - 1) / cap) < t || (t <= cap && g != t)) return false;
+  }
+  return true;
+}
+static_assert(rba_even_grid(920, 1024) == 920 && rba_even_grid(1024, 1024) == 1024 && rba_even_grid(2048, 1024) == 1024 &&
+              rba_even_grid(2049, 1024) == 683 && rba_even_grid(0, 1024) == 0, "persistent-grid rule");
+static_assert(rba_even_grid_covers(5000, 1024) && rba_even_grid_covers(300, 7) && rba_even_grid_covers(64, 1), "persistent-grid rule");
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of the function (one process per GPU is the deployment model, but a
+// process that touches a second device must not inherit the first one's "already set"): raise it when `bytes` exceeds the largest size set
+// so far on the current device.  `enabled` is the caller's record, one zero-initialised static array per kernel instantiation.
+template <typename KernelT>
+static inline int rba_dynamic_lds(KernelT kernel, size_t bytes, size_t (&enabled)[64]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
+  if (bytes > enabled[dev]) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return (int)e;
+    enabled[dev] = bytes;
+  }
+  return 0;
+}
+
 // 1 / (1 + e^-x): v_exp_f32 + v_rcp_f32, abs error <~ 1e-7 (ample for the 1e-4 score tolerance).
 __device__ __forceinline__ float rba_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __expf(-x));

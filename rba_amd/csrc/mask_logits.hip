@@ -71,8 +71,8 @@ int launch(const float* embed, const float* feat, float* out, int B, int Q, int 
   if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
   auto kern = mask_logits_kernel<QT, VEC>;
   if (shm > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return (int)e;
+    static size_t lds_enabled[64];
+    if (const int rc = rba_dynamic_lds(kern, shm, lds_enabled)) return rc;
   }
   hipLaunchKernelGGL(kern, grid, dim3(threads), shm, st, embed, feat, out, Q, C, N);
   return rba_launch_status();
@@ -181,13 +181,9 @@ int launch_mfma(const float* embed, const float* feat, float* out, int B, int Q,
   const size_t shm = (size_t)C * 113 * sizeof(float);
   if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
   auto kern = mask_logits_mfma_kernel<WAVES, PF>;
-  static size_t shm_enabled[64];                      // raise the dynamic-LDS cap once per instantiation AND device, not per launch
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-  if (shm > 64 * 1024 && shm > shm_enabled[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return (int)e;
-    shm_enabled[dev] = shm;
+  if (shm > 64 * 1024) {
+    static size_t lds_enabled[64];                    // raise the dynamic-LDS cap once per instantiation AND device, not per launch
+    if (const int rc = rba_dynamic_lds(kern, shm, lds_enabled)) return rc;
   }
   const int64_t per_block = 64LL * WAVES;
   dim3 grid((unsigned)((N + per_block - 1) / per_block), B);
@@ -339,19 +335,14 @@ template <int CT, int PF, int WAVES>
 int launch_h3(const float* embed, const float* feat, float* out, int B, int Q, int C, int64_t N, hipStream_t st) {
   const size_t shm = (size_t)(C / 32) * 7 * 2048;
   auto kern = mask_logits_h3_kernel<CT, PF, WAVES>;
-  static size_t shm_enabled[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-  if (shm > 64 * 1024 && shm > shm_enabled[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return (int)e;
-    shm_enabled[dev] = shm;
+  if (shm > 64 * 1024) {
+    static size_t lds_enabled[64];
+    if (const int rc = rba_dynamic_lds(kern, shm, lds_enabled)) return rc;
   }
   const int64_t wave_tiles = (N + 16 * CT - 1) / (16 * CT);
   if (wave_tiles > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  int64_t wgs = (wave_tiles + WAVES - 1) / WAVES;
-  const int64_t cap = B >= 256 ? 1 : 256 / B;                       // one workgroup per CU (LDS): persistent beyond that
-  if (wgs > cap) { const int64_t rounds = (wgs + cap - 1) / cap; wgs = (wgs + rounds - 1) / rounds; }
+  // one workgroup per CU (LDS): persistent beyond that
+  const int64_t wgs = rba_even_grid((wave_tiles + WAVES - 1) / WAVES, B >= 256 ? 1 : 256 / B);
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs, B), dim3(64 * WAVES), shm, st, embed, feat, out, Q, C, N, (int)wave_tiles);
   return rba_launch_status();
 }

@@ -184,14 +184,8 @@ int launch_bwd(const float* mask, const float* prob, const float* gscore, float*
   constexpr size_t SHM_MAX = (size_t)(160 + 16) * LDW * sizeof(float);
   if (shm > SHM_MAX) return (int)hipErrorInvalidValue;
   if (shm > 65536) {
-    static unsigned char done[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-    if (!done[dev]) {
-      const hipError_t e = hipFuncSetAttribute((const void*)rba_reduce_bwd_kernel<KMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SHM_MAX);
-      if (e != hipSuccess) return (int)e;
-      done[dev] = 1;
-    }
+    static size_t lds_enabled[64];
+    if (const int rc = rba_dynamic_lds(rba_reduce_bwd_kernel<KMAX>, SHM_MAX, lds_enabled)) return rc;
   }
   hipLaunchKernelGGL((rba_reduce_bwd_kernel<KMAX>), dim3((unsigned)tiles_of(HW)), dim3(TILE), shm, st, mask, prob, gscore, gmask, part, Q, K, HW,
                      mode, QC);

@@ -12,24 +12,14 @@ int k7_launch(float* x, float* y2, const float* g1, const float* b1, float eps1,
   const float scale = (float)(1.0 / sqrt(32.0));                                 // head_dim ** -0.5 (swin.py:103, 145)
   const dim3 grid(Wp / K7_WS, Hp / K7_WS, B), block(64 * K7_WAVES);
   constexpr size_t shm = k7_lds_bytes(C);
-  static unsigned char done[2][64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
+  static size_t lds_enabled[2][64];
   const unsigned char* im = reinterpret_cast<const unsigned char*>(img);
   if (y2) {
-    if (!done[1][dev]) {
-      const hipError_t e = hipFuncSetAttribute((const void*)swin_attn_block_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return (int)e;
-      done[1][dev] = 1;
-    }
+    if (const int rc = rba_dynamic_lds(swin_attn_block_kernel<C, true>, shm, lds_enabled[1])) return rc;
     hipLaunchKernelGGL((swin_attn_block_kernel<C, true>), grid, block, shm, st, x, y2, g1, b1, eps1, im, qkv_bias, bias_frag, proj_bias, g2, b2, eps2, H, W,
                        Hp, Wp, shift, scale, nullptr);
   } else {
-    if (!done[0][dev]) {
-      const hipError_t e = hipFuncSetAttribute((const void*)swin_attn_block_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return (int)e;
-      done[0][dev] = 1;
-    }
+    if (const int rc = rba_dynamic_lds(swin_attn_block_kernel<C, false>, shm, lds_enabled[0])) return rc;
     hipLaunchKernelGGL((swin_attn_block_kernel<C, false>), grid, block, shm, st, x, nullptr, g1, b1, eps1, im, qkv_bias, bias_frag, proj_bias, nullptr,
                        nullptr, 0.f, H, W, Hp, Wp, shift, scale, nullptr);
   }
@@ -45,14 +35,8 @@ int k7_launch_qkv(const float* x, void* out_frag, const float* g1, const float* 
   const float scale = (float)(1.0 / sqrt(32.0));
   const dim3 grid(Wp / K7_WS, Hp / K7_WS, B), block(64 * K7_WAVES);
   constexpr size_t shm = k7_lds_bytes(C, false);
-  static unsigned char done[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-  if (!done[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)swin_attn_block_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return (int)e;
-    done[dev] = 1;
-  }
+  static size_t lds_enabled[64];
+  if (const int rc = rba_dynamic_lds(swin_attn_block_kernel<C, false, false>, shm, lds_enabled)) return rc;
   hipLaunchKernelGGL((swin_attn_block_kernel<C, false, false>), grid, block, shm, st, const_cast<float*>(x), nullptr, g1, b1, eps1,
                      reinterpret_cast<const unsigned char*>(img), qkv_bias, bias_frag, nullptr, nullptr, nullptr, 0.f, H, W, Hp, Wp, shift, scale, out_frag);
   return rba_launch_status();

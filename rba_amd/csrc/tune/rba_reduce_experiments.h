@@ -11,6 +11,242 @@
 namespace rba_k1 {
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// Full-resolution forms that preceded rba_reduce_pk_kernel: the scalar formulation the compiler SLP-vectorises ("fast"), the LDS-DMA ring
+// ("dma") and the matrix pipe behind a wave-private LDS transposition ("wl").  tools/k1_sweep.py variants 0-14, 65-69, 90-94.
+template <int K, int VEC, bool SEM, bool ARG, int U, int WPS>
+__global__ __launch_bounds__(256, WPS) void rba_reduce_fast_kernel(const float* __restrict__ mask, const float* __restrict__ prob,
+                                                                 float* __restrict__ rba, float* __restrict__ sem,
+                                                                 int32_t* __restrict__ argmax, int Q, int64_t HW, int tiles, int mode) {
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t p0 = ((int64_t)tile * 256 + threadIdx.x) * VEC;
+    if (p0 >= HW) continue;
+    float acc[K][VEC];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) acc[k][i] = 0.f;
+    const float* mp = mask + p0;
+    float buf[U][VEC];
+#pragma unroll
+    for (int u = 0; u < U; ++u) load_vec<VEC>(mp + (int64_t)(u < Q ? u : Q - 1) * HW, buf[u]);
+    const int Qmain = Q / U * U;
+    for (int q0 = 0; q0 < Qmain; q0 += U) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int q = q0 + u;
+        float s[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) s[i] = rba_sigmoid(buf[u][i]);
+        const int qn = q + U < Q ? q + U : Q - 1;          // clamped prefetch (re-reads the last plane from L2)
+        load_vec<VEC>(mp + (int64_t)qn * HW, buf[u]);
+        const float* pq = prob + q * K;                    // wave-uniform -> scalar loads, SGPR operands
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float pk = pq[k];
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) acc[k][i] = fmaf(pk, s[i], acc[k][i]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {                          // tail: Q % U planes, already in the ring
+      const int q = Qmain + u;
+      if (q < Q) {
+        const float* pq = prob + q * K;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+          const float si = rba_sigmoid(buf[u][i]);
+#pragma unroll
+          for (int k = 0; k < K; ++k) acc[k][i] = fmaf(pq[k], si, acc[k][i]);
+        }
+      }
+    }
+    rba_epilogue<K, VEC, SEM, ARG>(acc, K, mode, rba, sem, argmax, p0, HW);
+  }
+}
+
+template <int K, int VEC, int U, int WPS>
+int launch_reduce_fast(const float* mask, const float* prob, float* rba, float* sem, int32_t* argmax, int Q,
+                       int64_t HW, hipStream_t st, int mode = 0) {
+  const int64_t per_block = 256 * (int64_t)VEC;
+  const int64_t tiles = (HW + per_block - 1) / per_block;
+  if (tiles > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  // 256 CUs x WPS resident 256-thread blocks (WPS waves per SIMD)
+  const int64_t grid = rba_even_grid(tiles, 256 * WPS);
+  with_output_form(sem != nullptr, argmax != nullptr, [&](auto SEM, auto ARG) {
+    hipLaunchKernelGGL((rba_reduce_fast_kernel<K, VEC, SEM.value, ARG.value, U, WPS>), dim3((unsigned)grid), dim3(256), 0, st, mask, prob, rba, sem,
+                       argmax, Q, HW, (int)tiles, mode);
+  });
+  return rba_launch_status();
+}
+
+// LDS-DMA ring formulation (4 pixels per thread): each wave streams its query planes through a private ring of R 1-KiB LDS
+// slots with global_load_lds_dwordx4 (no destination VGPRs, so R planes per wave are in flight instead of 2), reads its own
+// 16 bytes back with ds_read_b128 once the counted vmcnt says the plane has landed, and refills the slot.  No barrier: a lane
+// only ever reads what it loaded itself.  The compiler does not order a ds_read behind a pending LDS-DMA, so the wait is an
+// explicit s_waitcnt vmcnt(R - 1) and the read is inline asm.  Arithmetic identical to rba_reduce_pk_kernel (bit-identical).
+template <int K, bool SEM, bool ARG, int R, int WPS>
+__global__ __launch_bounds__(256, WPS) void rba_reduce_dma_kernel(const float* __restrict__ mask, const float* __restrict__ prob,
+                                                                float* __restrict__ rba, float* __restrict__ sem,
+                                                                int32_t* __restrict__ argmax, int Q, int64_t HW, int tiles, int mode) {
+  static_assert(R >= 2 && R <= 15, "vmcnt immediate");
+  extern __shared__ __attribute__((aligned(16))) unsigned char ring_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned char* wring = ring_raw + wave * (R * 1024);                       // this wave's ring
+  const uint32_t lds_lane = (uint32_t)(uintptr_t)(wring) + lane * 16;        // LDS byte address of this lane's 16 B in slot 0
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t p0 = ((int64_t)tile * 256 + threadIdx.x) * 4;              // HW % 1024 == 0 is required by the launcher
+    f32x2 a01[K], a23[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) a01[k] = a23[k] = (f32x2){0.f, 0.f};
+    const float* mp = mask + p0;
+#pragma unroll
+    for (int u = 0; u < R; ++u)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(mp + (int64_t)(u < Q ? u : Q - 1) * HW),
+                                       (__attribute__((address_space(3))) void*)(wring + u * 1024), 16, 0, 0);
+    for (int q0 = 0; q0 < Q; q0 += R) {
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        const int q = q0 + u;
+        if (q < Q) {                                                         // wave-uniform
+          f32x4 v;
+          // plane q is the oldest of the R DMAs in flight: wait until at most R - 1 are outstanding, then read it back
+          asm volatile("s_waitcnt vmcnt(%2)\n\tds_read_b128 %0, %1 offset:%3\n\ts_waitcnt lgkmcnt(0)"
+                       : "=v"(v) : "v"(lds_lane), "n"(R - 1), "n"(u * 1024) : "memory");
+          const int qn = q + R < Q ? q + R : Q - 1;                          // clamped refill keeps the count exact
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(mp + (int64_t)qn * HW),
+                                           (__attribute__((address_space(3))) void*)(wring + u * 1024), 16, 0, 0);
+          const f32x2 s01 = {rba_sigmoid(v.x), rba_sigmoid(v.y)};
+          const f32x2 s23 = {rba_sigmoid(v.z), rba_sigmoid(v.w)};
+          const float* pq = prob + q * K;
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            const f32x2 pk = {pq[k], pq[k]};
+            a01[k] = __builtin_elementwise_fma(pk, s01, a01[k]);
+            a23[k] = __builtin_elementwise_fma(pk, s23, a23[k]);
+          }
+        }
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // drain the clamped refills before the ring is reused
+    float acc[K][4];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { acc[k][0] = a01[k].x; acc[k][1] = a01[k].y; acc[k][2] = a23[k].x; acc[k][3] = a23[k].y; }
+    rba_epilogue<K, 4, SEM, ARG>(acc, K, mode, rba, sem, argmax, p0, HW);
+  }
+}
+
+template <int K, bool SEM, bool ARG, int R, int WPS>
+int launch_reduce_dma(const float* mask, const float* prob, float* rba, float* sem, int32_t* argmax, int Q, int64_t HW, int mode,
+                      hipStream_t st) {
+  if (HW % 1024) return (int)hipErrorInvalidValue;
+  const int64_t tiles = HW / 1024;
+  if (tiles > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  const int64_t grid = rba_even_grid(tiles, 256 * WPS);
+  hipLaunchKernelGGL((rba_reduce_dma_kernel<K, SEM, ARG, R, WPS>), dim3((unsigned)grid), dim3(256), 4 * R * 1024, st, mask, prob, rba, sem,
+                     argmax, Q, HW, (int)tiles, mode);
+  return rba_launch_status();
+}
+
+typedef float f32x4_m __attribute__((ext_vector_type(4)));
+
+// K1 on the matrix pipe with wave-private LDS transposition ("wl").  Diagnosis (profiles/r01_k1_bandwidth_probes.txt):
+// the VALU kernel is VALU-bound -- 76 fp32 FMAs + 4 sigmoids per lane per plane cost ~165 us whether or not they depend
+// on the loaded data, while its load pattern alone streams in 128 us.  So the contraction moves to the matrix pipe, but
+// the loads keep the good pattern (one wave-load = 1 KiB of ONE plane, ring of 2): a wave takes planes q..q+3 one at a
+// time, writes sigmoid(mask) for its 256 pixels into a 4 KiB wave-private LDS tile [4 planes][256 px] (no workgroup
+// barrier: LDS ops of one wave complete in order), then reads the MFMA B operand back transposed -- lane (k = lane/16,
+// j = lane%16) reads plane k, pixel 16 g + j -- and issues 16 v_mfma_f32_16x16x4_f32 (16 pixel groups x 4 queries, classes
+// 0..15 on the rows).  Classes 16..18 stay on VALU with scalar-register probabilities (the plane index is wave-uniform).
+template <int KX, int U>
+__global__ __launch_bounds__(256, 4) void rba_reduce_mfma_wl_kernel(const float* __restrict__ mask, const float* __restrict__ prob,
+                                                                    float* __restrict__ rba, int Q, int K, int64_t HW, int tiles) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int QP = (Q + 3) & ~3;
+  float* Pm = lds;                                                    // [QP][16] classes 0..15 (zero rows beyond Q)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, kk = lane >> 4;
+  float* Sw = lds + QP * 16 + wave * 1024;                            // this wave's [4][256] tile
+  for (int i = threadIdx.x; i < QP * 16; i += 256) {
+    const int q = i >> 4, c = i & 15;
+    Pm[i] = (q < Q && c < K) ? prob[q * K + c] : 0.f;
+  }
+  __syncthreads();
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t p0 = ((int64_t)tile * 4 + wave) * 256 + 4 * lane;   // this lane's 4 pixels (load side)
+    const bool active = p0 < HW;
+    const float* mp = mask + (active ? p0 : 0);
+    f32x4_m acc[16];
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = (f32x4_m){0.f, 0.f, 0.f, 0.f};
+    float ex[KX > 0 ? KX : 1][4];
+#pragma unroll
+    for (int e = 0; e < (KX > 0 ? KX : 1); ++e)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ex[e][i] = 0.f;
+    f32x4 buf[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) buf[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mp + (int64_t)(u < Q ? u : Q - 1) * HW));
+    for (int q0 = 0; q0 < QP; q0 += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int q = q0 + u;
+        const f32x4 m4 = buf[u % U];
+        const int qn = q + U < Q ? q + U : Q - 1;
+        buf[u % U] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(mp + (int64_t)qn * HW));
+        f32x4 sg;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sg[i] = rba_sigmoid(m4[i]);
+        *reinterpret_cast<f32x4*>(Sw + u * 256 + 4 * lane) = sg;
+        if (KX > 0 && q < Q) {                                        // wave-uniform
+          const float* pq = prob + q * K + 16;
+#pragma unroll
+          for (int e = 0; e < KX; ++e) {
+            const float pe = pq[e];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ex[e][i] = fmaf(pe, sg[i], ex[e][i]);
+          }
+        }
+      }
+      const float a = Pm[(q0 + kk) * 16 + l15];
+      const float* sb = Sw + kk * 256 + l15;
+#pragma unroll
+      for (int g = 0; g < 16; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, sb[16 * g], acc[g], 0, 0, 0);
+    }
+    // acc[g][r] = sem[class 4 kk + r][pixel 16 g + l15]: tanh-sum over the lane's 4 classes, then over the 4 lane groups
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      float tsum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tsum += rba_tanh(acc[g][r]);
+      tsum += __shfl_xor(tsum, 16, RBA_WAVE);
+      tsum += __shfl_xor(tsum, 32, RBA_WAVE);
+      if (kk == 0) Sw[16 * g + l15] = tsum;                           // re-use the tile: totals by pixel
+    }
+    const f32x4 t4 = *reinterpret_cast<const f32x4*>(Sw + 4 * lane);   // same wave wrote it: in-order LDS, no barrier needed
+    float r4[4] = {t4[0], t4[1], t4[2], t4[3]};
+    if (KX > 0) {
+#pragma unroll
+      for (int e = 0; e < KX; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r4[i] += rba_tanh(ex[e][i]);
+    }
+    if (active) *reinterpret_cast<f32x4*>(rba + p0) = (f32x4){-r4[0], -r4[1], -r4[2], -r4[3]};
+  }
+}
+
+template <int KX, int U>
+int launch_reduce_mfma_wl(const float* mask, const float* prob, float* rba, int Q, int K, int64_t HW, int bpc, hipStream_t st) {
+  const int64_t tiles = (HW + 1023) / 1024;
+  if (tiles > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  const int64_t grid = rba_even_grid(tiles, 256LL * bpc);
+  const size_t shm = ((size_t)((Q + 3) & ~3) * 16 + 4 * 1024) * sizeof(float);
+  if (shm > 64 * 1024) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((rba_reduce_mfma_wl_kernel<KX, U>), dim3((unsigned)grid), dim3(256), shm, st, mask, prob, rba, Q, K, HW, (int)tiles);
+  return rba_launch_status();
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // K1 on the matrix pipe without any transposition ("mx").  sem[k, p] = sum_q P[q, k] * sigmoid(mask[q, p]) is a GEMM with the
 // classes on M (19 padded to 32), the pixels on N and the queries on the reduction axis.  The B operand of
 // v_mfma_f32_32x32x16_bf16 wants, per lane, 8 CONSECUTIVE k (= queries) of ONE column (= pixel): lanes 0-31 hold k 0..7 and lanes
@@ -235,18 +471,6 @@ int launch_reduce_mx(const float* mask, const float* prob, float* rba, int Q, in
 // Step (tile, g): lane (l31, lh) loads planes q = 16 g + 8 lh + i, i < 8, at pixels 2 l31, 2 l31 + 1 of the tile (256 contiguous bytes
 // per plane and half-wave); sigmoid; pack (q = 2 j, 2 j + 1) pairs per pixel -> the f16x8 B operands of the two 32-pixel MFMA tiles;
 // A = the split class-probability fragment of query group g from LDS (built once per workgroup).
-template <typename KernelT>
-static inline int ensure_dynamic_lds_k1(KernelT kernel, size_t bytes, unsigned char (&done)[64]) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-  if (!done[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-    done[dev] = 1;
-  }
-  return 0;
-}
-
 typedef _Float16 h3k_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h3k_f16x2 __attribute__((ext_vector_type(2)));
 
@@ -546,9 +770,8 @@ int launch_reduce_tr(const float* mask, const float* prob, float* rba, int Q, in
   if (tiles > 0x7fffffffLL || Q > 256 || K > 32 || (HW & 3)) return (int)hipErrorInvalidValue;
   const int G = (Q + 31) / 32;
   const size_t dyn = (size_t)2 * 16 * 1056 + (size_t)G * 4 * 64 * 16;
-  static unsigned char done_attr[64] = {0};
-  int rc = ensure_dynamic_lds_k1(rba_reduce_tr_kernel<WPS, PROBE>, dyn, done_attr);
-  if (rc) return rc;
+  static size_t lds_enabled[64];
+  if (const int rc = rba_dynamic_lds(rba_reduce_tr_kernel<WPS, PROBE>, dyn, lds_enabled)) return rc;
   int64_t grid = 256 * WPS;
   grid = tiles < grid ? tiles : grid;
   grid = grid < 1 ? 1 : grid;
@@ -860,20 +1083,14 @@ int launch_reduce_m4(const float* mask, const float* prob, float* rba, float* se
   const size_t shm = (size_t)((Q + 3) / 4) * ((K + 3) / 4) * 64;
   if (shm > 32 * 1024) return (int)hipErrorInvalidValue;
   const int64_t cap = 256 * WPS;
-  int64_t grid = tiles;
   if (tiles <= cap) counters = nullptr;                             // one tile per workgroup: the static split (see launch_reduce_pk)
-  if (tiles > cap) {
-    const int64_t rounds = (tiles + cap - 1) / cap;
-    grid = counters ? cap : (tiles + rounds - 1) / rounds;
-  }
-#define RBA_L(S, A, D) \
-  hipLaunchKernelGGL((rba_reduce_m4_kernel<K, S, A, WPS, D, ABL>), dim3((unsigned)grid), dim3(256), shm, st, mask, prob, rba, sem, argmax, Q, HW, (int)tiles, mode, counters)
-  if (counters) {
-    if (sem && argmax) RBA_L(true, true, true); else if (sem) RBA_L(true, false, true); else if (argmax) RBA_L(false, true, true); else RBA_L(false, false, true);
-  } else {
-    if (sem && argmax) RBA_L(true, true, false); else if (sem) RBA_L(true, false, false); else if (argmax) RBA_L(false, true, false); else RBA_L(false, false, false);
-  }
-#undef RBA_L
+  const int64_t grid = counters ? cap : rba_even_grid(tiles, cap);
+  with_flag(counters != nullptr, [&](auto DYN) {
+    with_output_form(sem != nullptr, argmax != nullptr, [&](auto SEM, auto ARG) {
+      hipLaunchKernelGGL((rba_reduce_m4_kernel<K, SEM.value, ARG.value, WPS, DYN.value, ABL>), dim3((unsigned)grid), dim3(256), shm, st, mask, prob, rba,
+                         sem, argmax, Q, HW, (int)tiles, mode, counters);
+    });
+  });
   return rba_launch_status();
 }
 

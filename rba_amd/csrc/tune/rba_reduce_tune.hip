@@ -314,9 +314,7 @@ template <int KX, int U>
 int launch_reduce_mfma_wl2(const float* mask, const float* prob, float* rba, int Q, int K, int64_t HW, int bpc, hipStream_t st) {
   const int64_t tiles = (HW + 1023) / 1024;
   if (tiles > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  const int64_t cap = 256LL * bpc;
-  int64_t grid = tiles;
-  if (tiles > cap) { const int64_t rounds = (tiles + cap - 1) / cap; grid = (tiles + rounds - 1) / rounds; }
+  const int64_t grid = rba_even_grid(tiles, 256LL * bpc);
   const size_t shm = ((size_t)(((Q + 3) & ~3) + 4) * 16 + 4 * 2048) * sizeof(float);
   if (shm > 64 * 1024) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL((rba_reduce_mfma_wl2_kernel<KX, U>), dim3((unsigned)grid), dim3(256), shm, st, mask, prob, rba, Q, K, HW, (int)tiles);
@@ -353,9 +351,7 @@ template <int VEC, int U, int WPS, int TPB>
 int launch_bw_probe(const float* mask, float* rba, int Q, int64_t HW, hipStream_t st) {
   const int64_t per_block = TPB * (int64_t)VEC;
   const int64_t tiles = (HW + per_block - 1) / per_block;
-  const int64_t cap = 256LL * WPS * 256 / TPB;
-  int64_t grid = tiles;
-  if (tiles > cap) { const int64_t rounds = (tiles + cap - 1) / cap; grid = (tiles + rounds - 1) / rounds; }
+  const int64_t grid = rba_even_grid(tiles, 256LL * WPS * 256 / TPB);
   hipLaunchKernelGGL((rba_bw_probe_kernel<VEC, U, WPS, TPB>), dim3((unsigned)grid), dim3(TPB), 0, st, mask, rba, Q, HW, (int)tiles);
   return rba_launch_status();
 }
@@ -452,9 +448,7 @@ __global__ __launch_bounds__(256, WPS) void rba_valu_probe_kernel(const float* _
 template <int U, int WPS, bool DEP, int WORK = 0>
 int launch_valu_probe(const float* mask, const float* prob, float* rba, int Q, int64_t HW, hipStream_t st) {
   const int64_t tiles = (HW + 1023) / 1024;
-  const int64_t cap = 256LL * WPS;
-  int64_t grid = tiles;
-  if (tiles > cap) { const int64_t rounds = (tiles + cap - 1) / cap; grid = (tiles + rounds - 1) / rounds; }
+  const int64_t grid = rba_even_grid(tiles, 256LL * WPS);
   hipLaunchKernelGGL((rba_valu_probe_kernel<U, WPS, DEP, WORK>), dim3((unsigned)grid), dim3(256), 0, st, mask, prob, rba, Q, HW, (int)tiles);
   return rba_launch_status();
 }

@@ -185,6 +185,65 @@ def test_k1_up4_matrix_pipe_form_full_size_is_stable(ops, knobs):
     assert float((a - pk).abs().max()) < 2e-5
 
 
+K1_FULL = {"pk-19": (5, 19, 3, 8), "pk-20": (5, 20, 3, 8),                      # launch_reduce_pk, static split
+           "vec4-5": (5, 5, 3, 8), "unaligned-19": (5, 19, 3, 7),                 # launch_reduce<32, 4>, <32, 1>
+           "k65": (5, 65, 2, 3), "k133": (5, 133, 2, 3),                          # launch_reduce<80, 1>, <160, 1>
+           "pk-19-dynamic": (3, 19, 8, 131200)}                                   # 1025 tiles on 1024 slots: the smallest dynamic hand-out
+K1_FUSED = {"mx-19": (19, (7, 12), 0), "mx-20": (20, (7, 12), 0),                 # (K, crop, rba_k1_up4_variant): matrix pipe
+            "pk-19": (19, (7, 12), 2), "pk-20": (20, (7, 12), 2),                 # packed VALU
+            "pk-19-ragged": (19, (7, 10), 0),                                     # packed VALU, ragged rows
+            "generic-5": (5, (7, 12), 0), "generic-5-ragged": (5, (7, 10), 0),    # generic
+            "generic-19": (19, (7, 10), 1)}                                       # generic <19>
+
+
+@pytest.mark.parametrize("case", ["full-" + k for k in K1_FULL] + ["fused-" + k for k in K1_FUSED])
+def test_k1_every_launcher_in_every_output_form(ops, case, request):
+    """every K1 launcher with each of the four (sem_seg, argmax) requests: an output-form ladder that paired the flags wrongly would store
+    through a null pointer or leave a requested output unwritten.  Tolerances of test_k1_shapes / test_k1_up4_shapes."""
+    import ctypes
+    from rba_amd import _lib
+    kind, name = case.split("-", 1)
+    variant = 0
+    if kind == "full":
+        Q, K, H, W = K1_FULL[name]
+        sem_tol = 5e-6
+    else:
+        (K, crop, variant), Q = K1_FUSED[name], 5
+        sem_tol = 1e-5
+    g = torch.Generator().manual_seed(Q * 1000 + K)
+    prob = F.softmax(torch.randn(Q, K + 1, generator=g) * 3, -1)[:, :-1].contiguous()
+    if kind == "full":
+        mp = torch.randn(Q, H, W, generator=g) * 5
+        sem_r, rba_r, _ = ref_ops.rba_reduce_ordered(mp, prob)
+        x, p = dev(mp), dev(prob)
+        run = lambda ws, wa: ops.rba_reduce(x, p, ws, wa)
+    else:
+        low = torch.randn(Q, 2, 3, generator=g) * 5
+        sem_r, rba_r, _ = ref_ops.rba_reduce_ordered(ref_ops.upsample_bilinear(low[None], (8, 12))[0], prob)
+        sem_r, rba_r = sem_r[:, :crop[0], :crop[1]], rba_r[:crop[0], :crop[1]]
+        x, p = dev(low), dev(prob)
+        run = lambda ws, wa: ops.rba_reduce_up4(x, p, crop, ws, wa)
+    if variant:
+        request.getfixturevalue("knobs")
+        var = ctypes.c_int.in_dll(_lib.load(), "rba_k1_up4_variant")
+    try:
+        if variant:
+            var.value = variant
+        for ws_ in (False, True):
+            for wa_ in (False, True):
+                rba, sem, arg = run(ws_, wa_)
+                assert (sem is None) == (not ws_) and (arg is None) == (not wa_), (ws_, wa_)
+                e_rba, e_sem = maxerr(rba, rba_r), maxerr(sem, sem_r) if ws_ else 0.0
+                bad = argmax_ok(arg, sem_r)[0] if wa_ else 0
+                print(f"{case} sem={ws_} argmax={wa_}: rba {e_rba:.2e} sem {e_sem:.2e} argmax flips {bad}")
+                assert rba.shape == rba_r.shape and e_rba < 2e-5, (ws_, wa_)
+                assert e_sem < sem_tol, (ws_, wa_)
+                assert bad == 0, (ws_, wa_)
+    finally:
+        if variant:
+            var.value = 0
+
+
 def test_k1_up4_matrix_pipe_form_soak(ops):
     """2 000 launches of the score-only fused K1 at C2's and C5's maps, round-robin from three streams while a fourth
     stream runs a K6 GEMM loop; every output bit-equal to launch 0 of its map (tools/k1_soak.py reports the pixel pattern otherwise).
