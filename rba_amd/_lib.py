@@ -12,7 +12,6 @@ LIB_PATH = os.environ.get("RBA_HIP_LIB") or os.path.join(_HERE, "csrc", "librba_
 # (LIB_PATH) has no writable state besides rba_set_concurrent_streams' hint.  `use_library(KNOBS_LIB_PATH)` swaps it in for a block.
 KNOBS_LIB_PATH = os.path.join(_HERE, "csrc", "librba_hip_knobs.so")
 
-_c_f32p = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _vp = ctypes.c_void_p

@@ -33,6 +33,37 @@ def test_cabi_exports_every_declared_symbol():
     assert _lib.load().rba_hip_version() >= 100
 
 
+def header_source():
+    """include/rba_hip.h without comments -- also the /* ... */ inside argument lists"""
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "rba_hip.h")).read(), flags=re.S)
+
+
+def binding_type(decl):
+    """the ctypes type the binding gives one C argument / field declaration: any pointer travels as void*, scalars by their own type"""
+    if "*" in decl:
+        return ctypes.c_void_p
+    *base, _name = decl.replace("const ", " ").split()
+    return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}[" ".join(base)]
+
+
+def test_cabi_signatures_match_the_header_argument_by_argument():
+    """_lib.SIGNATURES is typed by hand beside the header: a c_int for an int64_t, or a missing argument, passes every test without a device and corrupts
+    the call on one.  Every prototype, every argument, the return types and the one struct are compared here."""
+    from rba_amd import _lib
+    src = header_source()
+    protos = {name: (ret, [] if args.strip() == "void" else args.split(","))
+              for ret, name, args in re.findall(r"\b(int|int64_t)\s+(rba_\w+)\s*\(([^()]*)\)\s*;", src)}
+    assert set(protos) == set(header_functions()) == set(_lib.SIGNATURES)
+    lib = _lib.load()
+    for name, (ret, args) in protos.items():
+        assert [binding_type(a) for a in args] == _lib.SIGNATURES[name], f"{name}: argtypes differ from the header"
+        assert (ret == "int64_t") == name.endswith(("_bytes", "_elems")), f"{name}: return type {ret}"
+        assert getattr(lib, name).restype is (ctypes.c_int64 if ret == "int64_t" else ctypes.c_int), name
+    body = re.search(r"typedef\s+struct\s*\{(.*?)\}\s*rba_token_linear_problem\s*;", src, flags=re.S).group(1)
+    fields = [(f.split()[-1].lstrip("*"), binding_type(f)) for f in body.split(";") if f.strip()]
+    assert fields == _lib.TokenLinearProblem._fields_
+
+
 def test_product_library_has_no_writable_state_and_the_knobs_build_does():
     """include/rba_hip.h: "no mutable global state except the launch-geometry hint".  The tuning knobs of csrc/knobs.h are compile-time constants in
     librba_hip.so (no data symbol named rba_*) and exported ints only in librba_hip_knobs.so, which tests / tools load to select kernel variants."""

@@ -26,7 +26,7 @@ def test_backward_is_declared_exported_and_bound():
         for n in NEW:
             assert hasattr(lib, n), f"{path} does not export {n}"
     for n in NEW:
-        assert n in _lib.SIGNATURES and len(_lib.SIGNATURES[n]) == 17       # 9 pointers, 7 ints, the stream
+        assert n in _lib.SIGNATURES                                         # argument lists: test_host_cpu, against the header
     assert _lib.load().rba_hip_version() == _lib.EXPECTED_ABI == 191
 
 

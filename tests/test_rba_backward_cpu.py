@@ -40,8 +40,7 @@ def test_libraries_export_the_entry_points(lib):
 
 def test_bindings_and_version():
     from rba_amd import _lib
-    assert len(_lib.SIGNATURES["rba_reduce_bwd_workspace_f32"]) == 4
-    assert len(_lib.SIGNATURES["rba_reduce_bwd_f32"]) == 12
+    assert {"rba_reduce_bwd_workspace_f32", "rba_reduce_bwd_f32"} <= set(_lib.SIGNATURES)       # argument lists: test_host_cpu, against the header
     assert _lib.EXPECTED_ABI == 191
 
 
