@@ -30,6 +30,7 @@
  *                                  (mask2former_transformer_decoder.py:106-118, 433, 483-487)
  *   rba_mask_logits_f32         <- torch.einsum("bqc,bchw->bqhw") (mask2former_transformer_decoder.py:479)
  *   rba_mask_logits_f16x3_f32   <- the same call site, f16x3 arithmetic
+ *   rba_mask_logits_bwd_f32     <- autograd's backward of that einsum (mask2former_transformer_decoder.py:479 under autograd)
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -170,6 +171,21 @@ int rba_mask_logits_f32(const float* embed, const float* feat, float* out, int B
  * beyond): the form the model uses in its default arithmetic mode.  Shapes outside Q <= 112, C % 32 == 0, C <= 256 run rba_mask_logits_f32. */
 int rba_mask_logits_f16x3_f32(const float* embed, const float* feat, float* out, int B, int Q, int C, int64_t N,
                               void* stream);
+
+/* K4 backward.  With grad_out [B,Q,N] = d loss / d out of the contraction above (any arithmetic mode of the forward):
+ *   grad_embed[b,q,c] = sum_n grad_out[b,q,n] feat[b,c,n]          grad_feat[b,c,n] = sum_q embed[b,q,c] grad_out[b,q,n]
+ * in exact fp32 (v_mfma_f32_16x16x4_f32; a plain VALU form when N % 4 != 0 or a pointer is not 16-byte aligned).  grad_embed [B,Q,C] and
+ * grad_feat [B,C,N] are each optional (NULL = not computed), at least one is required; `embed` is read only for grad_feat and `feat` only for
+ * grad_embed, and the one that is not read may be NULL.  Both are written element by element with plain stores, whatever they held before,
+ * and are bitwise reproducible from launch to launch: grad_embed is summed per slice of the pixel axis into `workspace` and then over the
+ * slices in a fixed order (no float atomics).  `workspace`: device memory owned by the caller, 4-byte aligned, at least
+ * rba_mask_logits_bwd_workspace_f32's byte count, needed only with grad_embed; its contents on entry do not matter.  Every shape of the
+ * forward is accepted (Q, N >= 0, C >= 1, 0 <= B <= 65535); B, Q or N of 0 is a no-op that returns 0.  A negative size, both outputs NULL, a
+ * NULL input that would be read, or grad_embed with a NULL or too small workspace returns hipErrorInvalidValue without a launch. */
+int rba_mask_logits_bwd_workspace_f32(int B, int Q, int C, int64_t N, int64_t* bytes);
+int rba_mask_logits_bwd_f32(const float* embed, const float* feat, const float* grad_out,
+                            float* grad_embed /* may be NULL */, float* grad_feat /* may be NULL */,
+                            int B, int Q, int C, int64_t N, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* K5.  Swin (shifted-)window attention core over a token map, fusing zero-pad to a multiple of the window,
  * cyclic shift, window partition, q*scale @ k^T + relative-position bias (+ shift mask), softmax, @ v,

@@ -115,6 +115,32 @@ class MaskFormer(nn.Module):
         outputs, sizes, padded = self._predict_outputs(batched_inputs)
         return outputs["pred_logits"], outputs["pred_masks"], sizes, padded
 
+    def finetune_outputs(self, batched_inputs):
+        """-> (outputs, image_sizes, padded (H,W)): _predict_outputs for the outlier-supervised fine-tune of the two prediction heads.  Backbone and
+        pixel decoder run under no_grad exactly as in `predict`; the predictor runs in the caller's grad mode with its ``differentiable_heads`` honoured, so
+        ``outputs["pred_logits"]`` / ``["pred_masks"]`` carry the bits `predict` gives and a graph over the ten head tensors
+        (``criterion.outlier_loss(outputs, targets)["outlier_loss"].backward()``).  Eager launches only: graph replay is never used here."""
+        predictor = self.sem_seg_head.predictor
+        if not getattr(predictor, "differentiable_heads", False):
+            raise ops.RbaHipError("finetune_outputs: set model.sem_seg_head.predictor.differentiable_heads = True first (without it the outputs "
+                                  "carry no autograd graph)")
+        with torch.no_grad():
+            pe = getattr(self.backbone, "patch_embed", None)
+            if (self.fused_front_end and pe is not None and hasattr(self.backbone, "forward_images") and pe.fused_ok()
+                    and all(x["image"].dim() == 3 and x["image"].shape[0] == 3 and x["image"].dtype in (torch.uint8, torch.float32)
+                            for x in batched_inputs)):
+                images = [to_device(x["image"], self.device).contiguous() for x in batched_inputs]      # the front end of _predict_outputs
+                sizes = [tuple(int(v) for v in im.shape[-2:]) for im in images]
+                d = self.size_divisibility
+                padded = ((max(s[0] for s in sizes) + d - 1) // d * d, (max(s[1] for s in sizes) + d - 1) // d * d)
+                features = self.backbone.forward_images(images, self._mean3, self._std3, *padded)
+            else:
+                batch, sizes = self.preprocess(batched_inputs)
+                padded = tuple(batch.shape[-2:])
+                features = self.backbone(batch)
+            mask_features, _, multi_scale_features = self.sem_seg_head.pixel_decoder.forward_features(features)
+        return predictor(multi_scale_features, mask_features), sizes, padded
+
     def _post(self, mask_cls, mask_pred, image_size, padded, want_sem_seg, want_argmax, score="rba"):
         """Up-sample (:294-299), semantic inference (:381-386), crop (:330-332), RbA (evaluate_ood.py:150)."""
         prob = _class_prob(mask_cls)

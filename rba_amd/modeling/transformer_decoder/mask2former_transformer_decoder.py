@@ -1,16 +1,19 @@
-"""Masked-attention transformer decoder, inference only (reference:
-transformer_decoder/mask2former_transformer_decoder.py:232-502, post-norm, dropout 0).  Same parameter names.
+"""Masked-attention transformer decoder (reference: transformer_decoder/mask2former_transformer_decoder.py:232-502, post-norm,
+dropout 0).  Same parameter names.  Inference only unless ``MultiScaleMaskedTransformerDecoder.differentiable_heads`` is set (see the class).
 
 MI355X dataflow: memory is kept batch-first [B, S, C]; the cross/self attention cores are the HIP kernel K3 with
 the ``sigmoid(mask) < 0.5`` threshold and the all-masked-row fix fused in (the bool [B*h, Q, S] mask of the
 reference is never materialised); mask logits are the HIP kernel K4; the bilinear down-sample that feeds the
 attention mask is the HIP resampler.
 """
+import contextlib
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from ... import ops
 from ...lru import ShapeCache, derived, source_key
@@ -35,6 +38,74 @@ def _qlinear(x, weight, bias=None, relu=False, x_add=None):
     for r0 in range(0, M, 128):
         ops.skinny_linear(x2[r0:r0 + 128], weight, bias, relu, x_add=None if a2 is None else a2[r0:r0 + 128], out=out[r0:r0 + 128])
     return out.view(tuple(x.shape[:-1]) + (weight.shape[0],))
+
+
+class MaskLogitsFunction(Function):
+    """``MaskLogitsFunction.apply(embed [B,Q,C], feat [B,C,h,w] | [B,C,N]) -> [B,Q,h,w] | [B,Q,N]``: ``ops.mask_logits`` in the current split mode
+    (the very bits of a direct call), differentiable once with respect to both tensors through ``ops.mask_logits_backward`` (exact fp32).  Only the
+    inputs the requested gradients read are saved -- ``feat`` for ``embed``'s gradient, ``embed`` for ``feat``'s; a gradient nobody asks for is
+    not computed."""
+
+    @staticmethod
+    def forward(ctx, embed, feat):
+        embed, feat = embed.contiguous(), feat.contiguous()
+        need_embed, need_feat = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ctx.save_for_backward(embed if need_feat else None, feat if need_embed else None)
+        return ops.mask_logits(embed, feat)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        embed, feat = ctx.saved_tensors
+        need_embed, need_feat = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_embed or need_feat):
+            return None, None
+        grad_out = grad_out.contiguous()                     # `out.sum().backward()` hands an expanded (stride 0) gradient
+        return ops.mask_logits_backward(embed, feat, grad_out, need_embed=need_embed, need_feat=need_feat)
+
+
+class _HeadLayerNormFunction(Function):
+    """``decoder_norm`` of the differentiable last head call: forward = the kernel of the inference path (``ops.add_layer_norm``), backward = torch's
+    LayerNorm backward on the [B*Q, C] query tensor, for weight and bias only -- the decoder-layer output receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        ctx.eps = eps
+        ctx.save_for_backward(x, weight, bias)
+        return ops.add_layer_norm(x, weight, bias, eps)[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, bias = ctx.saved_tensors
+        with torch.enable_grad():
+            w, b = weight.detach().requires_grad_(True), bias.detach().requires_grad_(True)
+            y = F.layer_norm(x, (x.shape[-1],), w, b, ctx.eps)
+        gw, gb = torch.autograd.grad(y, (w, b), grad_y)
+        return None, gw, gb, None
+
+
+class _HeadLinearFunction(Function):
+    """A query-side Linear (+ ReLU) of the differentiable last head call: forward = ``_qlinear`` (the skinny exact-fp32 kernel of the inference
+    path), backward = three small library GEMMs on [B*Q, C] rows by design, as in ``MSDeformAttn._forward_differentiable``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        y = _qlinear(x, weight, bias, relu)
+        ctx.relu = relu
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, y = ctx.saved_tensors
+        g = grad_y.reshape(-1, grad_y.shape[-1])
+        if ctx.relu:
+            g = g * (y.reshape(g.shape) > 0)
+        gx = (g @ weight).view(x.shape) if ctx.needs_input_grad[0] else None
+        gw = g.t() @ x.reshape(-1, x.shape[-1]) if ctx.needs_input_grad[1] else None
+        return gx, gw, g.sum(0) if ctx.needs_input_grad[2] else None, None
 
 
 class _MHAParams(nn.Module):
@@ -163,6 +234,17 @@ class BNReluConv(nn.Module):
 
 @TRANSFORMER_DECODER_REGISTRY.register()
 class MultiScaleMaskedTransformerDecoder(nn.Module):
+    """``differentiable_heads`` (attribute, default False) is the explicit opt-in to the outlier-supervised fine-tune, which trains the two
+    prediction heads only (FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP): with it set and grad mode on, the LAST ``forward_prediction_heads`` call of
+    ``forward`` (reference :472-479) builds an autograd graph over ``decoder_norm.{weight,bias}``, ``class_embed.{weight,bias}`` and the six
+    ``mask_embed`` tensors.  Its forward runs the kernels of the inference path -- ``pred_logits`` and ``pred_masks`` are bit-identical to it -- and
+    the contraction's backward is K4's backward kernel (``MaskLogitsFunction``).  ``mask_features`` and the decoder-layer output entering that
+    call receive no gradient: everything upstream of it runs under ``torch.no_grad`` and is not differentiable in this library; ``aux_outputs``
+    stay as in inference (detached; ``pred_logits`` only on the sparse path).  Otherwise -- whatever ``self.training`` or ``requires_grad`` of
+    the parameters say -- the inference path runs, which builds no autograd graph."""
+
+    differentiable_heads = False
+
     def __init__(self, arch):
         super().__init__()
         a = arch
@@ -220,6 +302,16 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         dec = ops.add_layer_norm(output.contiguous(), self.decoder_norm.weight, self.decoder_norm.bias, self.decoder_norm.eps)[1]
         return _qlinear(dec, self.class_embed.weight, self.class_embed.bias), self.mask_embed(dec).contiguous()
 
+    def _query_side_heads_differentiable(self, output):
+        """_query_side_heads with an autograd graph over its ten parameters (not over `output`): the same launches in the same order"""
+        n = self.decoder_norm
+        dec = _HeadLayerNormFunction.apply(output.detach().contiguous(), n.weight, n.bias, n.eps)
+        outputs_class = _HeadLinearFunction.apply(dec, self.class_embed.weight, self.class_embed.bias, False)
+        e = dec
+        for i, layer in enumerate(self.mask_embed.layers):
+            e = _HeadLinearFunction.apply(e, layer.weight, layer.bias, i < self.mask_embed.num_layers - 1)
+        return outputs_class, e.contiguous()
+
     def _initial_query_side(self, B, device):
         """The prediction heads BEFORE the first layer (reference :427-430) see `query_feat.weight` -- learnt parameters, not the image: decoder_norm, class_embed
         and the three mask_embed Linears of that call are constants of the checkpoint.  Computed once per (weights version, batch size) with the same kernels
@@ -250,6 +342,10 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         logits [B,Q,h*w] (reference :472-489; the threshold itself happens inside K3).  When only the attention mask is
         consumed (every call but the last) the mask logits are evaluated just at the 2x2 source pixels each attention
         cell interpolates -- the same arithmetic on 4*h*w instead of H*W/16 columns."""
+        if self.differentiable_heads and torch.is_grad_enabled() and need_masks and not need_attn_mask:
+            # the last call of a fine-tune forward (see the class): live heads, never the cached initial ones
+            outputs_class, mask_embed = self._query_side_heads_differentiable(output)
+            return outputs_class, MaskLogitsFunction.apply(mask_embed, mask_features.detach()), None
         if query_side is not None:
             outputs_class, mask_embed = query_side
         else:
@@ -282,9 +378,27 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
 
     def forward(self, x, mask_features, mask=None):
         """x: list of [B,C,h_l,w_l]; mask_features [B,md,H/4,W/4] -> dict(pred_logits, pred_masks, aux_outputs)
-        (reference :398-470)."""
+        (reference :398-470).  With ``differentiable_heads`` and grad mode on, everything but the last head call runs under no_grad."""
         assert len(x) == self.num_feature_levels
         del mask
+        frozen = torch.no_grad if self.differentiable_heads and torch.is_grad_enabled() else contextlib.nullcontext
+        with frozen():
+            output, mask_features, side, predictions_class, predictions_mask = self._decode(x, mask_features)
+        cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side)
+        out = {
+            "pred_logits": cls,
+            "pred_masks": msk,
+            "aux_outputs": [({"pred_logits": a, "pred_masks": b} if b is not None else {"pred_logits": a})
+                            for a, b in zip(predictions_class, predictions_mask)],
+        }
+        if self.ood_prediction:
+            with frozen():
+                out["ood_pred"] = self.ood_pred(mask_features)                       # reference :467-468
+        return out
+
+    def _decode(self, x, mask_features):
+        """Everything of forward before its last head call -> (decoder-layer output [B,Q,C], contiguous mask_features, the cached query side of that
+        call (only a decoder without layers has one), class and mask predictions of the intermediate calls)."""
         src, pos, size_list = [], [], []
         B = x[0].shape[0]
         for i in range(self.num_feature_levels):
@@ -301,9 +415,11 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             output, side0 = self.query_feat.weight[None].expand(B, -1, -1).contiguous(), None
         mask_features = mask_features.contiguous()
         predictions_class, predictions_mask = [], []
+        if self.num_layers == 0:
+            return output, mask_features, side0, predictions_class, predictions_mask
         gathered = {}
-        cls, msk, attn_logits = self.forward_prediction_heads(output, mask_features, size_list[0], self.num_layers > 0,
-                                                              need_masks=self.num_layers == 0, gathered=gathered, query_side=side0)
+        cls, msk, attn_logits = self.forward_prediction_heads(output, mask_features, size_list[0], True, need_masks=False, gathered=gathered,
+                                                              query_side=side0)
         predictions_class.append(cls)
         predictions_mask.append(msk)
         for i in range(self.num_layers):
@@ -311,18 +427,10 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             output = self.transformer_cross_attention_layers[i](output, src[li], attn_logits, pos[li], query_embed)   # memory + pos: inside the key projection
             output = self.transformer_self_attention_layers[i](output, query_embed)
             output = self.transformer_ffn_layers[i](output)
-            last = i == self.num_layers - 1
+            if i == self.num_layers - 1:
+                break
             cls, msk, attn_logits = self.forward_prediction_heads(
-                output, mask_features, size_list[(i + 1) % self.num_feature_levels], need_attn_mask=not last, need_masks=last,
-                gathered=gathered)
+                output, mask_features, size_list[(i + 1) % self.num_feature_levels], need_attn_mask=True, need_masks=False, gathered=gathered)
             predictions_class.append(cls)
             predictions_mask.append(msk)
-        out = {
-            "pred_logits": predictions_class[-1],
-            "pred_masks": predictions_mask[-1],
-            "aux_outputs": [({"pred_logits": a, "pred_masks": b} if b is not None else {"pred_logits": a})
-                            for a, b in zip(predictions_class[:-1], predictions_mask[:-1])],
-        }
-        if self.ood_prediction:
-            out["ood_pred"] = self.ood_pred(mask_features)                           # reference :467-468
-        return out
+        return output, mask_features, None, predictions_class, predictions_mask

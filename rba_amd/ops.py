@@ -164,7 +164,7 @@ def _mode(score):
     return SCORE_MODES[score]
 
 
-_K1_WORKSPACES = {}       # (device, stream, "tiles" | "grad_prob") -> buffer
+_K1_WORKSPACES = {}       # (device, stream, "tiles" | "grad_prob" | "grad_embed") -> buffer
 
 
 def _stream_workspace(kind, device, words, alloc, dtype):
@@ -367,6 +367,46 @@ def mask_logits(embed, feat, mode=None):
     _launch("rba_mask_logits_f16x3_f32" if (_split_mode() if mode is None else mode) == "f16x3" else "rba_mask_logits_f32",
             _p(embed), _p(feat), _p(out), B, Q, C, math.prod(sp))
     return out
+
+
+def _k4_bwd_workspace(device, nbytes):
+    """K4 backward's per-slice grad_embed partial sums: per (device, stream) and grow-only like K1 backward's; the kernel writes every word it later reads."""
+    return _stream_workspace("grad_embed", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+
+
+@_hip_op
+def mask_logits_backward(embed, feat, grad_out, need_embed=True, need_feat=True):
+    """K4 backward.  embed [B,Q,C], feat [B,C,N] or [B,C,h,w] (mask_logits' inputs), grad_out [B,Q] + feat.shape[2:] = dL/d out ->
+    (grad_embed [B,Q,C] | None, grad_feat like feat | None), the gradients of the einsum (mask2former_transformer_decoder.py:479 under autograd)
+    in exact fp32 whatever mode the forward ran in.  Both are bitwise reproducible from launch to launch.  The operand a call does not read
+    (embed without need_feat, feat without need_embed) may be None."""
+    if not (need_embed or need_feat):
+        raise RbaHipError("mask_logits_backward: at least one of need_embed / need_feat")
+    if need_feat or embed is not None:
+        _chk(embed, "embed", dim=3)
+    if need_embed or feat is not None:
+        _chk(feat, "feat")
+    _chk(grad_out, "grad_out")
+    if grad_out.dim() not in (3, 4):
+        raise RbaHipError("grad_out must be [B,Q,N] or [B,Q,h,w]")
+    B, Q = grad_out.shape[:2]
+    sp = tuple(grad_out.shape[2:])
+    C = embed.shape[2] if embed is not None else feat.shape[1]
+    _shaped(embed, "embed", (B, Q, C), optional=True)
+    _shaped(feat, "feat", (B, C) + sp, optional=True)
+    N = math.prod(sp)
+    dev = grad_out.device
+    ws, ws_bytes = None, 0
+    if need_embed:
+        n = ctypes.c_int64(0)
+        _lib.check(_query("rba_mask_logits_bwd_workspace_f32", B, Q, C, N, ctypes.addressof(n)), "rba_mask_logits_bwd_workspace_f32")
+        ws_bytes = int(n.value)
+        ws = _k4_bwd_workspace(dev, ws_bytes)
+    alloc = torch.empty if B and Q and N else torch.zeros          # an empty reduction: the entry point is a no-op, the gradient is 0
+    grad_embed = alloc((B, Q, C), dtype=torch.float32, device=dev) if need_embed else None
+    grad_feat = alloc((B, C) + sp, dtype=torch.float32, device=dev) if need_feat else None
+    _launch("rba_mask_logits_bwd_f32", _p(embed), _p(feat), _p(grad_out), _p(grad_embed), _p(grad_feat), B, Q, C, N, _p(ws), ws_bytes)
+    return grad_embed, grad_feat
 
 
 @_hip_op
