@@ -31,6 +31,10 @@
  *   rba_mask_logits_f32         <- torch.einsum("bqc,bchw->bqhw") (mask2former_transformer_decoder.py:479)
  *   rba_mask_logits_f16x3_f32   <- the same call site, f16x3 arithmetic
  *   rba_mask_logits_bwd_f32     <- autograd's backward of that einsum (mask2former_transformer_decoder.py:479 under autograd)
+ *   rba_point_sample_f32        <- detectron2's point_sample (mask2former/modeling/criterion.py:216-234, matcher.py:122-132)
+ *   rba_mask_point_loss_fwd_f32 <- point_sample of the matched masks + sigmoid_ce_loss + dice_loss (criterion.py:23-68, 230-239);
+ *   rba_mask_point_loss_bwd_f32    autograd's backward of the three
+ *   rba_match_cost_f32          <- the cost matrix of HungarianMatcher.memory_efficient_forward (matcher.py:105-149)
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -186,6 +190,51 @@ int rba_mask_logits_bwd_workspace_f32(int B, int Q, int C, int64_t N, int64_t* b
 int rba_mask_logits_bwd_f32(const float* embed, const float* feat, const float* grad_out,
                             float* grad_embed /* may be NULL */, float* grad_feat /* may be NULL */,
                             int B, int Q, int C, int64_t N, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* K8.  Point-sampled mask losses and the matcher's cost (docs/kernels/K8.md).  Sampling rule of all four entry points = detectron2's point_sample,
+ * F.grid_sample(x, 2 c - 1, mode="bilinear", padding_mode="zeros", align_corners=False): a point c = (x, y) in normalised coordinates reads the
+ * plane [h,w] at the pixel coordinates (c_x w - 0.5, c_y h - 0.5) from its four neighbours floor / floor + 1; a neighbour outside the plane
+ * contributes 0 and is never read.  Coordinates are finite floats; nothing else is assumed about them.
+ *
+ * rba_point_sample_f32: out[n,p] = planes[plane_index[n]] sampled at coords[n,p] (shared_coords = 0, coords [N,P,2]) or at coords[p]
+ * (shared_coords = 1, coords [P,2]); planes [num_planes,h,w]; plane_index [N] int64 with repeats allowed, NULL = row n reads plane n (then
+ * N <= num_planes).  A row whose index lies outside [0, num_planes) reads nothing and gets NaN.  N == 0 or P == 0: success without a launch.
+ * N <= 65535; h w < 2^31.  Bitwise reproducible. */
+int rba_point_sample_f32(const float* planes, const int64_t* plane_index /* may be NULL */, const float* coords, float* out,
+                         int64_t num_planes, int N, int h, int w, int P, int shared_coords, void* stream);
+
+/* The fused mask loss of N matched masks.  Mask n is plane plane_index[n] of pred_masks [num_planes,h,w] (num_planes = B Q; no copy of the matched
+ * planes is made), sampled at coords[n] [N,P,2] to logits x[n,p] and reduced against labels [N,P] (fractional labels allowed) to
+ *   sums[n] = ( sum_p max(x,0) - x t + log1p(exp(-|x|)),  a = sum_p sigmoid(x) t,  b = sum_p sigmoid(x),  c = sum_p t )          [N,4]
+ *   losses[0] = loss_mask = sum_n (sums[n,0] / P) / num_masks         losses[1] = loss_dice = sum_n [1 - (2 a + 1) / (b + c + 1)] / num_masks
+ * One workgroup per mask and a fixed-order finish: sums and both losses are bitwise reproducible from launch to launch (no float atomics).
+ *
+ * rba_mask_point_loss_bwd_f32: grad_masks [num_planes,h,w] = d (g_m loss_mask + g_d loss_dice) / d pred_masks with g_m = *grad_loss_mask and
+ * g_d = *grad_loss_dice read on the device (no host synchronisation; one of the two may be NULL = 0); x and sigmoid(x) are recomputed from the
+ * forward's inputs and `sums`.  On return (stream order) grad_masks is fully defined whatever it held before: it is zero-filled here
+ * (hipMemsetAsync on `stream`), so the planes no mask names are exactly 0, and each named plane then receives its P x 4 bilinear contributions
+ * with float atomics -- its last bits depend on arrival order and may differ from launch to launch.  The matcher gives a plane to at most one
+ * mask; planes named twice receive the sum of both masks' contributions.  A mask whose index lies outside [0, num_planes) gives NaN sums and
+ * losses and writes no gradient.  1 <= N <= 65535, P >= 1, num_masks > 0, h w < 2^31; anything else, or a NULL pointer other than one of the two
+ * upstream gradients, returns hipErrorInvalidValue without a launch. */
+int rba_mask_point_loss_fwd_f32(const float* pred_masks, const int64_t* plane_index, const float* coords, const float* labels,
+                                float* sums, float* losses, int64_t num_planes, int N, int h, int w, int P, float num_masks, void* stream);
+int rba_mask_point_loss_bwd_f32(const float* pred_masks, const int64_t* plane_index, const float* coords, const float* labels,
+                                const float* sums, const float* grad_loss_mask /* may be NULL */, const float* grad_loss_dice /* may be NULL */,
+                                float* grad_masks, int64_t num_planes, int N, int h, int w, int P, float num_masks, void* stream);
+
+/* The matcher's cost matrix of one image in one call: pred_masks [Q,h,w] and tgt_masks [T,H,W] sampled at the shared coords [P,2] to x[q,p], t[m,p],
+ *   cost[q,m] = w_mask ( sum_p softplus(x) - sum_p x t ) / P  +  w_class ( - cls_prob[q, tgt_ids[m]] )
+ *             + w_dice ( 1 - (2 sum_p sigmoid(x) t + 1) / (sum_p sigmoid(x) + sum_p t + 1) )                                          [Q,T]
+ * (batch_sigmoid_ce_loss's pos t + neg (1 - t) is softplus(x) - x t).  cls_prob [Q,K1] (K1 = K + 1 classes), tgt_ids [T] int64 in [0, K1); a target
+ * whose id lies outside gets a NaN column.  Neither sampled tensor goes to memory: per-slice partial sums over the points go to `workspace` and are
+ * added in a fixed order (no float atomics), so the matrix is bitwise reproducible from launch to launch.  `workspace`: device memory owned by
+ * the caller, 4-byte aligned, at least rba_match_cost_workspace_f32's byte count; its contents on entry do not matter.  Q, T, P, K1 >= 1 of any
+ * size (the target axis is walked in blocks); h w, H W < 2^31; anything else returns hipErrorInvalidValue without a launch. */
+int rba_match_cost_workspace_f32(int Q, int T, int P, int64_t* bytes);
+int rba_match_cost_f32(const float* pred_masks, const float* tgt_masks, const float* coords, const float* cls_prob, const int64_t* tgt_ids,
+                       float* cost, int Q, int T, int P, int h, int w, int H, int W, int K1, float w_mask, float w_class, float w_dice,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* K5.  Swin (shifted-)window attention core over a token map, fusing zero-pad to a multiple of the window,
  * cyclic shift, window partition, q*scale @ k^T + relative-position bias (+ shift mask), softmax, @ v,

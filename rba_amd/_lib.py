@@ -40,6 +40,11 @@ SIGNATURES = {
     "rba_mask_logits_f16x3_f32": [_vp, _vp, _vp, _i, _i, _i, _i64, _vp],
     "rba_mask_logits_bwd_workspace_f32": [_i, _i, _i, _i64, _vp],
     "rba_mask_logits_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _i64, _vp],
+    "rba_point_sample_f32": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp],
+    "rba_mask_point_loss_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, ctypes.c_float, _vp],
+    "rba_mask_point_loss_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, ctypes.c_float, _vp],
+    "rba_match_cost_workspace_f32": [_i, _i, _i, _vp],
+    "rba_match_cost_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],

@@ -1,9 +1,15 @@
-"""The reference's outlier-supervision loss (``SetCriterion.outlier_loss``, mask2former/modeling/criterion.py:435-553) on the HIP kernels:
-the score of criterion.py:449-465 -- softmax / sigmoid, ``einsum("bqc,bqhw->bchw")``, tanh-sum | logsumexp | sum -- is K1 at the mask
-resolution (``ops.rba_reduce``), and its gradient is K1's backward kernel (``ops.rba_reduce_backward``).  Everything around it is small
-and stays torch with autograd: the class softmax ([Q, K+1] per image), the ``align_corners=True`` upsample of the one-channel score map and
-the masked means.  This is what the outlier-supervised fine-tune (``..._1dl_coco_mix_finetune.yaml``: backbone, pixel decoder and the
-transformer decoder but its two heads frozen) differentiates; the matcher, the other losses and the trainer are not part of this library.
+"""The fine-tune recipe's criterion (``SetCriterion``, mask2former/modeling/criterion.py) on the HIP kernels.
+
+``outlier_loss`` (criterion.py:435-553): the score of criterion.py:449-465 -- softmax / sigmoid, ``einsum("bqc,bqhw->bchw")``, tanh-sum |
+logsumexp | sum -- is K1 at the mask resolution (``ops.rba_reduce``), and its gradient is K1's backward kernel (``ops.rba_reduce_backward``).
+Everything around it is small and stays torch with autograd: the class softmax ([Q, K+1] per image), the ``align_corners=True`` upsample of
+the one-channel score map and the masked means.
+
+``loss_masks`` (criterion.py:194-243): the uncertainty oversampling, the label sampling and the two point-sampled losses with their scatter
+backward are K8 (``ops.point_sample``, ``ops.mask_point_loss``, ``ops.mask_point_loss_backward``); no ``grid_sample`` call.  ``loss_labels``
+(criterion.py:174-192) is plain torch.  ``SetCriterion`` is the reference's ``forward`` over these three losses behind a matcher
+(``rba_amd.modeling.matcher``); the four PEBAL / DenseHybrid losses, gradients into ``aux_outputs``, data mappers and the trainer are not
+part of this library.
 """
 import torch
 import torch.nn.functional as F
@@ -105,3 +111,230 @@ def outlier_loss_from_cfg(cfg):
     if kw["func"] not in FUNCS:
         raise ValueError(f"outlier_loss: func {kw['func']!r} is not built (built: {list(FUNCS)})")
     return functools.partial(outlier_loss, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the point-sampled mask losses (K8)
+class MaskPointLossFunction(Function):
+    """``MaskPointLossFunction.apply(pred_masks [B,Q,h,w], plane_index [N], point_coords [N,P,2], point_labels [N,P], num_masks) ->
+    (loss_mask, loss_dice)``: ``ops.mask_point_loss`` (the very bits of a direct call), differentiable once with respect to ``pred_masks`` only
+    through ``ops.mask_point_loss_backward``.  Mask n is plane ``plane_index[n]`` of ``pred_masks.view(B * Q, h, w)``.  Saved: the inputs and
+    the per-mask sums [N,4].  N = 0: both losses are 0, the gradient is zeros, and no kernel is launched."""
+
+    @staticmethod
+    def forward(ctx, pred_masks, plane_index, point_coords, point_labels, num_masks):
+        if pred_masks.dim() != 4:
+            raise ops.RbaHipError(f"MaskPointLossFunction: pred_masks [B,Q,h,w], got {tuple(pred_masks.shape)}")
+        ctx.num_masks, ctx.empty = float(num_masks), plane_index.numel() == 0
+        if ctx.empty:
+            ctx.like = (pred_masks.shape, pred_masks.device)
+            zero = torch.zeros((), dtype=torch.float32, device=pred_masks.device)
+            return zero, zero.clone()
+        pred_masks, point_coords, point_labels = pred_masks.contiguous(), point_coords.contiguous(), point_labels.contiguous()
+        losses, sums = ops.mask_point_loss(pred_masks, plane_index, point_coords, point_labels, ctx.num_masks)
+        ctx.save_for_backward(pred_masks, plane_index, point_coords, point_labels, sums)
+        return losses[0], losses[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_mask, grad_dice):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        if ctx.empty:
+            return torch.zeros(ctx.like[0], dtype=torch.float32, device=ctx.like[1]), None, None, None, None
+        pred_masks, plane_index, point_coords, point_labels, sums = ctx.saved_tensors
+        grad = ops.mask_point_loss_backward(pred_masks, plane_index, point_coords, point_labels, sums, ctx.num_masks,
+                                            grad_mask.contiguous(), grad_dice.contiguous())
+        return grad, None, None, None, None
+
+
+def select_uncertain_points(pred_masks, plane_index, candidates, num_uncertain):
+    """The selection of detectron2's ``get_uncertain_point_coords_with_randomness`` with the reference's uncertainty -|x| (criterion.py:76-90):
+    mask n = plane ``plane_index[n]`` of pred_masks [B,Q,h,w] is sampled at candidates[n] [N,R,2] (``ops.point_sample``) and the
+    ``num_uncertain`` candidates of smallest |logit| are returned, most uncertain first -> [N, num_uncertain, 2]."""
+    with torch.no_grad():
+        logits = ops.point_sample(pred_masks.detach().contiguous(), candidates.contiguous(), plane_index)
+        idx = torch.topk(-logits.abs(), k=num_uncertain, dim=1)[1]
+        return torch.gather(candidates, 1, idx[:, :, None].expand(-1, -1, 2))
+
+
+def draw_point_candidates(N, num_points, oversample_ratio, importance_sample_ratio, device, generator=None):
+    """The random numbers of ``uncertain_point_coords``, drawn before anything is selected -> (candidates [N, int(num_points * oversample_ratio), 2],
+    random points [N, num_points - int(importance_sample_ratio * num_points), 2]), uniform in [0, 1)."""
+    num_uncertain = int(importance_sample_ratio * num_points)
+    candidates = torch.rand(N, int(num_points * oversample_ratio), 2, device=device, generator=generator)
+    return candidates, torch.rand(N, num_points - num_uncertain, 2, device=device, generator=generator)
+
+
+def uncertain_point_coords(pred_masks, plane_index, num_points, oversample_ratio, importance_sample_ratio, generator=None):
+    """detectron2's ``get_uncertain_point_coords_with_randomness`` (point_rend/point_features.py) for the matched masks: of
+    ``int(num_points * oversample_ratio)`` uniform candidates per mask the ``int(importance_sample_ratio * num_points)`` most uncertain, followed by
+    uniform points up to ``num_points`` -> [N, num_points, 2] in [0, 1)."""
+    if oversample_ratio < 1 or not 0 <= importance_sample_ratio <= 1:
+        raise ValueError("uncertain_point_coords: oversample_ratio >= 1 and 0 <= importance_sample_ratio <= 1")
+    candidates, rest = draw_point_candidates(plane_index.numel(), num_points, oversample_ratio, importance_sample_ratio, pred_masks.device, generator)
+    chosen = select_uncertain_points(pred_masks, plane_index, candidates, int(importance_sample_ratio * num_points))
+    return torch.cat([chosen, rest], dim=1)
+
+
+def _flat_rows(per_image, sizes, device):
+    """one int64 index vector per image into that image's `sizes[b]` rows -> their rows in the images' concatenation"""
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + int(n))
+    return torch.cat([i.to(torch.int64) + o for i, o in zip(per_image, offs)]).to(device)
+
+
+def _padded_masks(masks, dtype, device):
+    """nested_tensor_from_tensor_list (utils/misc.py) on the images' [T_i,H_i,W_i] masks: one [sum T_i, max H, max W] tensor, zero-padded bottom / right"""
+    H, W = max(m.shape[-2] for m in masks), max(m.shape[-1] for m in masks)
+    out = torch.zeros((sum(m.shape[0] for m in masks), H, W), dtype=dtype, device=device)
+    o = 0
+    for m in masks:
+        out[o:o + m.shape[0], :m.shape[-2], :m.shape[-1]] = m.to(device=device, dtype=dtype)
+        o += m.shape[0]
+    return out
+
+
+def loss_masks(outputs, targets, indices, num_masks, *, num_points, oversample_ratio, importance_sample_ratio, point_coords=None, generator=None):
+    """``SetCriterion.loss_masks`` (criterion.py:194-243).  outputs["pred_masks"] [B,Q,h,w]; targets[i]["masks"] [T_i,H_i,W_i] (zero-padded to the
+    batch's largest H x W); indices = the matcher's [(idx_i, idx_j)]; ``point_coords`` [N,P,2] replaces the random oversampling (tests)
+    -> {"loss_mask", "loss_dice"}.  No matched mask in the batch: both are 0 with a zero gradient and no kernel is launched."""
+    pred = outputs["pred_masks"]
+    B, Q = pred.shape[:2]
+    dev = pred.device
+    plane_index = _flat_rows([i for i, _ in indices], [Q] * B, dev)
+    if plane_index.numel() == 0:
+        lm, ld = MaskPointLossFunction.apply(pred, plane_index, None, None, num_masks)
+        return {"loss_mask": lm, "loss_dice": ld}
+    with torch.no_grad():
+        tgt_index = _flat_rows([j for _, j in indices], [t["masks"].shape[0] for t in targets], dev)
+        tgt = _padded_masks([t["masks"] for t in targets], pred.dtype, dev)
+        if point_coords is None:
+            point_coords = uncertain_point_coords(pred, plane_index, num_points, oversample_ratio, importance_sample_ratio, generator)
+        point_coords = point_coords.contiguous()
+        point_labels = ops.point_sample(tgt, point_coords, tgt_index)
+    lm, ld = MaskPointLossFunction.apply(pred, plane_index, point_coords, point_labels, num_masks)
+    return {"loss_mask": lm, "loss_dice": ld}
+
+
+def loss_labels(outputs, targets, indices, *, num_classes, eos_coef):
+    """``SetCriterion.loss_labels`` (criterion.py:174-192), plain torch: cross entropy over all B Q queries against the matched targets' labels
+    (unmatched: the no-object class ``num_classes``, weighted ``eos_coef``) -> {"loss_ce"}."""
+    logits = outputs["pred_logits"].float()
+    dev = logits.device
+    classes = torch.full(logits.shape[:2], num_classes, dtype=torch.int64, device=dev)
+    for b, (t, (i, j)) in enumerate(zip(targets, indices)):
+        classes[b, i.to(dev)] = t["labels"].to(dev)[j.to(dev)]
+    weight = torch.ones(num_classes + 1, dtype=logits.dtype, device=dev)
+    weight[-1] = eos_coef
+    return {"loss_ce": F.cross_entropy(logits.transpose(1, 2), classes, weight)}
+
+
+BUILT_LOSSES = ("labels", "masks", "outlier")
+REFERENCE_LOSSES = BUILT_LOSSES + ("smoothness", "sparsity", "gambler", "densehybrid")
+
+
+class SetCriterion(torch.nn.Module):
+    """The reference's ``SetCriterion`` (criterion.py:99-172, 569-624) over the losses built here: "labels", "masks" and "outlier"; "smoothness",
+    "sparsity", "gambler" and "densehybrid" raise ValueError.  ``outlier`` = the keyword settings of ``outlier_loss``.  ``forward(outputs,
+    targets)`` matches the final outputs, computes num_masks (all-reduced over the process group when one is initialised, clamped to 1), runs
+    every loss, then the same per ``aux_outputs`` entry i with the key suffix ``_{i}``."""
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio, importance_sample_ratio, **outlier):
+        super().__init__()
+        for name in losses:
+            if name not in BUILT_LOSSES:
+                raise ValueError(f"SetCriterion: loss {name!r} is " + ("not built" if name in REFERENCE_LOSSES else "unknown") + f" (built: {list(BUILT_LOSSES)})")
+        unknown = set(outlier) - {"target", "score_norm", "func", "inlier_upper_threshold", "outlier_lower_threshold"}
+        if unknown:
+            raise TypeError(f"SetCriterion: unknown outlier settings {sorted(unknown)}")
+        self.num_classes, self.matcher, self.weight_dict, self.eos_coef, self.losses = num_classes, matcher, dict(weight_dict), eos_coef, list(losses)
+        self.num_points, self.oversample_ratio, self.importance_sample_ratio = num_points, oversample_ratio, importance_sample_ratio
+        self.outlier = dict(outlier)
+
+    def get_loss(self, loss, outputs, targets, indices, num_masks, point_coords=None, generator=None):
+        if loss == "labels":
+            return loss_labels(outputs, targets, indices, num_classes=self.num_classes, eos_coef=self.eos_coef)
+        if loss == "masks":
+            if "pred_masks" not in outputs:
+                raise ValueError("SetCriterion: an outputs entry without pred_masks")
+            return loss_masks(outputs, targets, indices, num_masks, num_points=self.num_points, oversample_ratio=self.oversample_ratio,
+                              importance_sample_ratio=self.importance_sample_ratio, point_coords=point_coords, generator=generator)
+        return outlier_loss(outputs, targets, **self.outlier)
+
+    def forward(self, outputs, targets, matcher_point_coords=None, loss_point_coords=None, generator=None):
+        """``matcher_point_coords`` [P,2] and ``loss_point_coords`` [N,P,2] replace the random points of the matcher and of loss_masks (tests)."""
+        final = {k: v for k, v in outputs.items() if k != "aux_outputs"}
+        if "pred_masks" not in final:
+            raise ValueError("SetCriterion: outputs without pred_masks")
+        for i, aux in enumerate(outputs.get("aux_outputs", ())):
+            if "pred_masks" not in aux:
+                raise ValueError(f"SetCriterion: aux_outputs[{i}] has no pred_masks")
+        match = lambda out: self.matcher(out, targets, point_coords=matcher_point_coords, generator=generator)
+        indices = match(final)
+        dev = final["pred_masks"].device
+        num_masks = torch.as_tensor([sum(len(t["labels"]) for t in targets)], dtype=torch.float, device=dev)
+        world = 1
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(num_masks)
+            world = torch.distributed.get_world_size()
+        num_masks = torch.clamp(num_masks / world, min=1).item()
+        losses = {}
+        for loss in self.losses:
+            losses.update(self.get_loss(loss, final, targets, indices, num_masks, loss_point_coords, generator))
+        for i, aux in enumerate(outputs.get("aux_outputs", ())):
+            indices = match(aux)
+            for loss in self.losses:
+                losses.update({f"{k}_{i}": v for k, v in self.get_loss(loss, aux, targets, indices, num_masks, loss_point_coords, generator).items()})
+        return losses
+
+    def weighted(self, losses):
+        """maskformer_model.py:283-288: every loss times its weight; a loss without a weight is dropped"""
+        return {k: v * self.weight_dict[k] for k, v in losses.items() if k in self.weight_dict}
+
+
+# mask2former/config.py (add_maskformer2_config), the values in force after the file's last assignment of each key
+_CRITERION_DEFAULTS = {"DEEP_SUPERVISION": True, "NO_OBJECT_WEIGHT": 0.1, "CLASS_WEIGHT": 1.0, "DICE_WEIGHT": 1.0, "MASK_WEIGHT": 20.0, "DEC_LAYERS": 6,
+                       "TRAIN_NUM_POINTS": 112 * 112, "OVERSAMPLE_RATIO": 3.0, "IMPORTANCE_SAMPLE_RATIO": 0.75, "OUTLIER_SUPERVISION": False,
+                       "OUTLIER_WEIGHT": 1.0, "MATCHER": "HungarianMatcher", "SMOOTHNESS_LOSS": False, "SMOOTHNESS_WEIGHT": 3e-6, "SPARSITY_LOSS": False,
+                       "SPARSITY_WEIGHT": 5e-4, "GAMBLER_LOSS": False, "GAMBLER_WEIGHT": 1.0, "DENSE_HYBRID_LOSS": False, "DENSE_HYBRID_WEIGHT": 1.0,
+                       "NUM_OBJECT_QUERIES": 100}
+
+
+def criterion_from_cfg(cfg):
+    """The criterion a config selects (maskformer_model.py:112-195): matcher, weight_dict (with the ``_{i}`` copies of DEEP_SUPERVISION), the list of
+    losses, the point-sampling settings and, with OUTLIER_SUPERVISION, ``outlier_loss_from_cfg``'s settings.  A loss that is not built raises
+    ValueError here."""
+    from .matcher import FixedMatcher, HungarianMatcher
+    model = cfg.get("MODEL", {})
+    mf = model.get("MASK_FORMER", {})
+    v = {k: mf.get(k, d) for k, d in _CRITERION_DEFAULTS.items()}
+    num_classes = int(model.get("SEM_SEG_HEAD", {}).get("NUM_CLASSES", 19))
+    if v["MATCHER"] == "HungarianMatcher":
+        matcher = HungarianMatcher(cost_class=v["CLASS_WEIGHT"], cost_mask=v["MASK_WEIGHT"], cost_dice=v["DICE_WEIGHT"], num_points=int(v["TRAIN_NUM_POINTS"]))
+    elif v["MATCHER"] == "FixedMatcher":
+        if num_classes != int(v["NUM_OBJECT_QUERIES"]):
+            raise ValueError("When using FixedMatcher, number of object queries must be equal to number of classes")
+        matcher = FixedMatcher()
+    else:
+        raise ValueError(f"Given Matcher ({v['MATCHER']}) is not defined")
+    weight_dict = {"loss_ce": v["CLASS_WEIGHT"], "loss_mask": v["MASK_WEIGHT"], "loss_dice": v["DICE_WEIGHT"], "smoothness_loss": v["SMOOTHNESS_WEIGHT"],
+                   "sparsity_loss": v["SPARSITY_WEIGHT"], "outlier_loss": v["OUTLIER_WEIGHT"], "gambler_loss": v["GAMBLER_WEIGHT"],
+                   "densehybrid_loss": v["DENSE_HYBRID_WEIGHT"]}
+    if v["DEEP_SUPERVISION"]:
+        weight_dict.update({f"{k}_{i}": w for i in range(int(v["DEC_LAYERS"]) - 1) for k, w in list(weight_dict.items())})
+    losses = ["labels", "masks"]
+    if v["GAMBLER_LOSS"]:
+        losses = ["gambler"]
+    if v["DENSE_HYBRID_LOSS"]:
+        losses = ["densehybrid"]
+    if v["SMOOTHNESS_LOSS"]:
+        losses.append("smoothness")
+    if v["SPARSITY_LOSS"]:
+        losses.append("sparsity")
+    outlier = {}
+    if v["OUTLIER_SUPERVISION"]:
+        losses.append("outlier")
+        outlier = outlier_loss_from_cfg(cfg).keywords
+    return SetCriterion(num_classes, matcher, weight_dict, float(v["NO_OBJECT_WEIGHT"]), losses, int(v["TRAIN_NUM_POINTS"]), float(v["OVERSAMPLE_RATIO"]),
+                        float(v["IMPORTANCE_SAMPLE_RATIO"]), **outlier)

@@ -409,6 +409,130 @@ def mask_logits_backward(embed, feat, grad_out, need_embed=True, need_feat=True)
     return grad_embed, grad_feat
 
 
+def _planes(t, name):
+    """Mask planes [..., h, w] (at least one leading axis) -> (number of planes, h, w)."""
+    _chk(t, name)
+    if t.dim() < 3 or t.shape[-1] < 1 or t.shape[-2] < 1:
+        raise RbaHipError(f"{name} must be [..., h, w] with h, w >= 1, got shape {tuple(t.shape)}")
+    return math.prod(t.shape[:-2]), t.shape[-2], t.shape[-1]
+
+
+def _point_coords(coords, name, N):
+    """Normalised (x, y) points: [N,P,2], or [1,P,2] / [P,2] shared by all N rows -> (P, shared)."""
+    _chk(coords, name)
+    if coords.dim() == 2:
+        coords = coords[None]
+    if coords.dim() != 3 or coords.shape[2] != 2 or coords.shape[0] not in (1, N):
+        raise RbaHipError(f"{name} must be [{N},P,2], [1,P,2] or [P,2], got shape {tuple(coords.shape)}")
+    return coords.shape[1], int(coords.shape[0] != N)
+
+
+def _plane_index(index, N=None):
+    _chk(index, "plane_index", dtype=torch.int64, dim=1)
+    if N is not None and index.numel() != N:
+        raise RbaHipError(f"plane_index must have {N} elements, got {index.numel()}")
+    return index.numel()
+
+
+def _grid_rows_ok(who, N):
+    if N > 65535:
+        raise RbaHipError(f"{who}: at most 65535 rows per call, got {N}")
+
+
+@_hip_op
+def point_sample(planes, coords, plane_index=None):
+    """K8.  detectron2's point_sample (F.grid_sample(x, 2 c - 1, align_corners=False), bilinear, zero padding): planes [..., h, w] fp32, coords
+    [N,P,2] (x, y) or shared [1,P,2] / [P,2], plane_index int64 [N] choosing each row's plane (repeats allowed; None: row n reads plane n)
+    -> [N,P].  A row whose index names no plane is NaN."""
+    M, h, w = _planes(planes, "planes")
+    N = M if plane_index is None else _plane_index(plane_index)
+    _grid_rows_ok("point_sample", N)
+    P, shared = _point_coords(coords, "coords", N)
+    out = torch.empty((N, P), dtype=torch.float32, device=planes.device)
+    _launch("rba_point_sample_f32", _p(planes), _p(plane_index), _p(coords), _p(out), M, N, h, w, P, shared)
+    return out
+
+
+def _mask_point_loss_args(pred_masks, plane_index, point_coords, point_labels, num_masks):
+    M, h, w = _planes(pred_masks, "pred_masks")
+    N = _plane_index(plane_index)
+    _grid_rows_ok("mask_point_loss", N)
+    _chk(point_coords, "point_coords", dim=3)
+    P = point_coords.shape[1]
+    _shaped(point_coords, "point_coords", (N, P, 2))
+    _shaped(point_labels, "point_labels", (N, P))
+    if N < 1 or P < 1 or not float(num_masks) > 0:
+        raise RbaHipError(f"mask_point_loss: needs N >= 1 masks, P >= 1 points and num_masks > 0, got N = {N}, P = {P}, num_masks = {num_masks}")
+    return M, N, h, w, P
+
+
+@_hip_op
+def mask_point_loss(pred_masks, plane_index, point_coords, point_labels, num_masks):
+    """K8.  The reference's two mask losses (criterion.py:230-239: point_sample + sigmoid_ce_loss + dice_loss) of N matched masks in one call.
+    pred_masks [..., h, w] (e.g. [B,Q,h,w]); mask n is plane plane_index[n] (int64 [N]) of its flattened leading axes, sampled at
+    point_coords[n] [N,P,2] against point_labels [N,P] -> (losses [2] = (loss_mask, loss_dice), sums [N,4] = per-mask (bce, sigma t, sigma, t)
+    sums for the backward).  Both are bitwise reproducible from launch to launch."""
+    M, N, h, w, P = _mask_point_loss_args(pred_masks, plane_index, point_coords, point_labels, num_masks)
+    dev = pred_masks.device
+    sums = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    losses = torch.empty((2,), dtype=torch.float32, device=dev)
+    _launch("rba_mask_point_loss_fwd_f32", _p(pred_masks), _p(plane_index), _p(point_coords), _p(point_labels), _p(sums), _p(losses),
+            M, N, h, w, P, float(num_masks))
+    return losses, sums
+
+
+@_hip_op
+def mask_point_loss_backward(pred_masks, plane_index, point_coords, point_labels, sums, num_masks, grad_loss_mask=None, grad_loss_dice=None):
+    """K8.  mask_point_loss's inputs and `sums`, and the two upstream gradients as one-element fp32 device tensors (one may be None = 0; they are
+    read on the device) -> the gradient like pred_masks: planes no mask names are exactly 0, the others are summed with float atomics and may
+    differ in the last bits from launch to launch."""
+    M, N, h, w, P = _mask_point_loss_args(pred_masks, plane_index, point_coords, point_labels, num_masks)
+    _shaped(sums, "sums", (N, 4))
+    if grad_loss_mask is None and grad_loss_dice is None:
+        raise RbaHipError("mask_point_loss_backward: at least one of grad_loss_mask / grad_loss_dice")
+    for g, name in ((grad_loss_mask, "grad_loss_mask"), (grad_loss_dice, "grad_loss_dice")):
+        if g is not None and _chk(g, name).numel() != 1:
+            raise RbaHipError(f"{name} must have one element, got shape {tuple(g.shape)}")
+    grad = torch.empty(pred_masks.shape, dtype=torch.float32, device=pred_masks.device)
+    _launch("rba_mask_point_loss_bwd_f32", _p(pred_masks), _p(plane_index), _p(point_coords), _p(point_labels), _p(sums), _p(grad_loss_mask),
+            _p(grad_loss_dice), _p(grad), M, N, h, w, P, float(num_masks))
+    return grad
+
+
+def _match_cost_workspace(device, nbytes):
+    """match_cost's per-slice partial sums: per (device, stream) and grow-only like K1 / K4 backward's; the kernel writes every word it later reads."""
+    return _stream_workspace("match_cost", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+
+
+@_hip_op
+def match_cost(pred_masks, tgt_masks, coords, cls_prob, tgt_ids, cost_mask=1.0, cost_class=1.0, cost_dice=1.0):
+    """K8.  The matcher's cost matrix of one image (matcher.py:105-149): pred_masks [Q,h,w], tgt_masks [T,H,W] fp32, the shared points coords
+    [P,2] or [1,P,2], cls_prob [Q,K+1] = softmax of the class logits, tgt_ids int64 [T] -> [Q,T] =
+    cost_mask * batch_sigmoid_ce + cost_class * (-cls_prob[:, tgt_ids]) + cost_dice * batch_dice.  Bitwise reproducible from launch to launch.
+    tgt_ids outside [0, K] are refused: that check reads one flag back from the device (the matcher needs the matrix on the host anyway)."""
+    _chk(pred_masks, "pred_masks", dim=3)
+    _chk(tgt_masks, "tgt_masks", dim=3)
+    _chk(cls_prob, "cls_prob", dim=2)
+    _chk(tgt_ids, "tgt_ids", dtype=torch.int64, dim=1)
+    Q, h, w = pred_masks.shape
+    T, H, W = tgt_masks.shape
+    P, _ = _point_coords(coords, "coords", 1)
+    K1 = cls_prob.shape[1]
+    if coords.numel() != 2 * P or cls_prob.shape[0] != Q or tgt_ids.numel() != T or min(Q, T, P, K1, h, w, H, W) < 1:
+        raise RbaHipError(f"match_cost: pred_masks [Q,h,w], tgt_masks [T,H,W], coords [P,2], cls_prob [Q,K+1], tgt_ids [T], all sizes >= 1; got "
+                          f"{tuple(pred_masks.shape)}, {tuple(tgt_masks.shape)}, {tuple(coords.shape)}, {tuple(cls_prob.shape)}, {tuple(tgt_ids.shape)}")
+    if bool(((tgt_ids < 0) | (tgt_ids >= K1)).any()):
+        raise RbaHipError(f"match_cost: tgt_ids must lie in [0, {K1 - 1}]")
+    dev = pred_masks.device
+    n = ctypes.c_int64(0)
+    _lib.check(_query("rba_match_cost_workspace_f32", Q, T, P, ctypes.addressof(n)), "rba_match_cost_workspace_f32")
+    ws = _match_cost_workspace(dev, int(n.value))
+    cost = torch.empty((Q, T), dtype=torch.float32, device=dev)
+    _launch("rba_match_cost_f32", _p(pred_masks), _p(tgt_masks), _p(coords), _p(cls_prob), _p(tgt_ids), _p(cost), Q, T, P, h, w, H, W, K1,
+            float(cost_mask), float(cost_class), float(cost_dice), _p(ws), int(n.value))
+    return cost
+
+
 @_hip_op
 def swin_bias_fragments(rel_bias, window_size):
     """[nH,N,N] gathered relative-position bias -> the MFMA-fragment-ordered copy K5 reads with coalesced loads."""
