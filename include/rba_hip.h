@@ -404,6 +404,30 @@ int rba_split_linear_nchw_out_gn_f16x3_f32(const float* x, const float* mr, cons
                                            const void* weight_packed, const float* bias, float* out, int64_t M, int N, int K,
                                            int rows_per_image, void* stream);
 
+/* The mask heads of the masked decoder WITHOUT the 1/4-resolution mask-feature map (docs/kernels/K4.md).  Nothing stands between
+ * `self.mask_features(...)` (pixel_decoder/msdeformattn.py:362, a plain Conv2d(conv_dim, mask_dim, 1)) and
+ * `torch.einsum("bqc,bchw->bqhw", mask_embed, mask_features)` (mask2former_transformer_decoder.py:479), so
+ *     pred_masks[b,q,p] = sum_k (E W)[b,q,k] g[b,p,k] + (E bias)[b,q],   g = ReLU(GroupNorm(y)).
+ *
+ * rba_split_linear_nchw_out_gn_rows_f16x3_f32: rba_split_linear_nchw_out_gn_f16x3_f32 with
+ *   - row_index [B][R] int32 or NULL: output row r of image b is source row row_index[b][r] of that image's P rows (out [B][N][R]) -- what
+ *     `mask_features.flatten(2).index_select(2, plan)` picks from the full map (the 4 h w pixels the attention mask of :481-489 samples),
+ *     bit for bit.  Values outside [0, P) are clamped (no out-of-bounds read); callers validate a plan once.  NULL: R == P, rows in order;
+ *   - weight_image_stride (bytes, a multiple of 16) and bias_image_stride (elements): 0 = one weight image / bias for every image; otherwise
+ *     image b reads weight_packed + b * weight_image_stride and bias + b * bias_image_stride (the composed operand below).
+ *   x [B*P][K] raw convolution rows; mr, gamma, beta, G, relu as above; N >= 1 (only N channel planes are written); K % 32 == 0,
+ *   (K / G) % 4 == 0, P % 128 == 0, R % 128 == 0, P * K < 2^30.
+ * rba_compose_query_operand_f16x2: embed [B][Q][C] fp32, weight [C][K] (the convolution's matrix), bias [C] or NULL -> packed = B planes of
+ *   512 * K bytes, each exactly rba_split_weight_f16x2's image of the [Q, K] matrix embed[b] * weight (rows Q .. 127 zero), and
+ *   bias_q [B][Q] = embed[b] * bias (zeros for NULL).  fp32 FMAs over four quarters of c, added in a fixed order: deterministic.  A product beyond f16's range
+ *   packs to +-inf: the projection's row is NaN (the f16x3 overflow contract).  Q <= 128, C <= 256, C % 4 == 0, K % 32 == 0, B <= 65535. */
+int rba_split_linear_nchw_out_gn_rows_f16x3_f32(const float* x, const float* mr, const float* gamma, const float* beta, int G, int relu,
+                                                const void* weight_packed, int64_t weight_image_stride, const float* bias,
+                                                int bias_image_stride, const int32_t* row_index, float* out, int B, int P, int R, int N,
+                                                int K, void* stream);
+int rba_compose_query_operand_f16x2(const float* embed, const float* weight, const float* bias, void* packed, float* bias_q, int B, int Q,
+                                    int C, int K, void* stream);
+
 /* 3x3 / stride 1 / pad 1 convolution over NHWC activations as an implicit GEMM on the same kernel:
  * x [B,H,W,C] -> out [B,H,W,N]; weight_packed = rba_split_weight_bf16x3 of the [N, 9*C] matrix w[n][(3*ky + kx)*C + c]
  * (conv weight [N,C,3,3] permuted to [N,3,3,C]); bias [N] or NULL.  C % 32 == 0.

@@ -72,6 +72,8 @@ SIGNATURES = {
     "rba_conv3x3_nhwc_f16x3_split_in_gn_moments_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "rba_group_norm_nhwc_merge_f32": [_vp, _vp, _i, _i, _i, ctypes.c_float, _vp],
     "rba_split_linear_nchw_out_gn_f16x3_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "rba_split_linear_nchw_out_gn_rows_f16x3_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "rba_compose_query_operand_f16x2": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "rba_conv3x3_nhwc_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_conv3x3_nhwc_f16x3_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_conv3x3_nhwc_f16x3_split_in_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

@@ -53,6 +53,82 @@ extern "C" int rba_split_weight_f16x2(const float* weight, void* packed, int N, 
   return rba_launch_status();
 }
 
+// The composed query operand of the final mask head (docs/kernels/K4.md): nothing stands between the mask-feature 1 x 1 convolution
+// (pixel_decoder/msdeformattn.py:362) and einsum("bqc,bchw->bqhw") (mask2former_transformer_decoder.py:479), so
+//   pred_masks[b,q,p] = sum_k (E W)[b,q,k] g[b,p,k] + (E bias)[b,q]
+// and the projection can contract the pixels with E W directly.  A workgroup owns 32 rows x the two 16-byte units per row of ONE sub-stage of image b's plane (the
+// layout of split_weight_f16x2_kernel for an [N = Q, K] matrix, rows Q .. 127 zero).  Its four waves each sum a quarter of c = 0 .. C - 1 (fp32 FMAs, ascending c)
+// for the unit's eight (E W)[b, r, k0 .. k0 + 7]; the quarters are added through LDS as (q0 + q1) + (q2 + q3): a fixed order, deterministic.  (One thread per
+// unit over all of C was a 256-step dependent chain on 17 workgroups: 31.3 us at Q = 100, C = K = 256; this form 23.6 us, docs/measurements.md.)  Then the same (h, l) split -- a value beyond f16's range
+// packs to +-inf and the projection's row is NaN.  Workgroup (K / 16, b, 0) leaves bias_q[b][q] = sum_c E[b,q,c] bias[c] (zeros without a bias).
+// grid (K / 16 + 1, B, 4), 256 threads.
+__global__ __launch_bounds__(256) void compose_query_operand_kernel(const float* __restrict__ E, const float* __restrict__ W, const float* __restrict__ bias,
+                                                                    u32x4_t* __restrict__ packed, float* __restrict__ bias_q, int Q, int C, int K) {
+  __shared__ float part[3][64][8];
+  const int S = K >> 4, b = blockIdx.y, tid = threadIdx.x;
+  if ((int)blockIdx.x == S) {
+    if (blockIdx.z == 0 && tid < Q) {
+      const float* e = E + ((int64_t)b * Q + tid) * C;
+      float acc = 0.f;
+      if (bias)
+        for (int c = 0; c < C; ++c) acc = fmaf(e[c], bias[c], acc);
+      bias_q[(int64_t)b * Q + tid] = acc;
+    }
+    return;
+  }
+  const int s = blockIdx.x, lane = tid & 63, chunk = tid >> 6, slot = lane & 1, r = 32 * blockIdx.z + (lane >> 1);
+  const int h = slot ^ ((r >> 3) & 1);
+  const int k0 = 32 * (s >> 1) + 16 * h + 8 * (s & 1);
+  const int CC = ((C + 15) >> 4) << 2;                                             // channels per quarter, a multiple of 4 (C % 4 == 0)
+  const int c0 = chunk * CC, c1 = c0 + CC < C ? c0 + CC : C;
+  f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+  if (r < Q) {
+    const float* e = E + ((int64_t)b * Q + r) * C;
+    const float* w = W + k0;
+    for (int c = c0; c < c1; c += 4) {
+      const f32x4 e4 = *reinterpret_cast<const f32x4*>(e + c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + (int64_t)(c + i) * K), w1 = *reinterpret_cast<const f32x4*>(w + (int64_t)(c + i) * K + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          lo[j] = fmaf(e4[i], w0[j], lo[j]);
+          hi[j] = fmaf(e4[i], w1[j], hi[j]);
+        }
+      }
+    }
+  }
+  if (chunk > 0) {
+    *reinterpret_cast<f32x4*>(&part[chunk - 1][lane][0]) = lo;
+    *reinterpret_cast<f32x4*>(&part[chunk - 1][lane][4]) = hi;
+  }
+  __syncthreads();
+  if (chunk > 0) return;
+  const f32x4 l1 = *reinterpret_cast<const f32x4*>(&part[0][lane][0]), h1 = *reinterpret_cast<const f32x4*>(&part[0][lane][4]);
+  const f32x4 l2 = *reinterpret_cast<const f32x4*>(&part[1][lane][0]), h2 = *reinterpret_cast<const f32x4*>(&part[1][lane][4]);
+  const f32x4 l3 = *reinterpret_cast<const f32x4*>(&part[2][lane][0]), h3 = *reinterpret_cast<const f32x4*>(&part[2][lane][4]);
+  lo = (lo + l1) + (l2 + l3);
+  hi = (hi + h1) + (h2 + h3);
+  f16x8_t p0, p1;
+  split_h3(lo, hi, p0, p1);
+  u32x4_t* dst = packed + ((int64_t)b * S + s) * 512 + r * 2 + slot;
+  dst[0] = __builtin_bit_cast(u32x4_t, p0);
+  dst[256] = __builtin_bit_cast(u32x4_t, p1);
+}
+
+// embed [B][Q][C], weight [C][K] (the convolution's [mask_dim, conv_dim] matrix), bias [C] or NULL -> packed: B planes of 512 K bytes each in exactly
+// rba_split_weight_f16x2's layout for the [Q, K] matrix embed[b] weight, and bias_q [B][Q].  Q <= 128, C <= 256, C % 4 == 0, K % 32 == 0.  One launch.
+extern "C" int rba_compose_query_operand_f16x2(const float* embed, const float* weight, const float* bias, void* packed, float* bias_q, int B, int Q, int C,
+                                               int K, void* stream) {
+  RBA_CHECK_ARG(B >= 0 && Q >= 1 && Q <= 128 && C >= 4 && C <= 256 && (C % 4) == 0 && K >= 32 && (K % 32) == 0 && B <= 65535);
+  if (B == 0) return 0;
+  RBA_CHECK_ARG(embed && weight && packed && bias_q && (((uintptr_t)embed | (uintptr_t)weight | (uintptr_t)packed) & 15) == 0);
+  rba_begin();
+  hipLaunchKernelGGL(compose_query_operand_kernel, dim3((unsigned)(K >> 4) + 1, (unsigned)B, 4), dim3(256), 0, (hipStream_t)stream, embed, weight, bias,
+                     reinterpret_cast<u32x4_t*>(packed), bias_q, Q, C, K);
+  return rba_launch_status();
+}
+
 extern "C" int rba_split_linear_f16x3_f32(const float* x, const void* weight_packed, const float* bias, float* out, int64_t M, int N,
                                           int K, int act, void* stream) {
   RBA_CHECK_ARG(N >= 1 && act >= 0 && act <= 2);

@@ -25,3 +25,33 @@ extern "C" int rba_split_linear_nchw_out_gn_f16x3_f32(const float* x, const floa
   a.gn = GnFold{mr, gamma, beta, G, K / G, relu ? 1 : 0};
   return rba_gemm_status(h3_wide(M, N) ? launch_h3l<0, 4, H3_NCHW | H3_GNF>(a) : launch_h3l<0, 2, H3_NCHW | H3_GNF>(a));
 }
+
+// The two mask heads of the masked decoder on the DEFERRED mask-feature operand (docs/kernels/K4.md): the entry above with an optional per-image row index
+// and optional per-image operands.
+//   row_index [B][R] int32 (or NULL: R == P, every row in order): output row r of image b is the projection of x[b P + row_index[b][r]] -- the columns
+//     `mask_features.flatten(2).index_select(2, plan)` would pick from the full map (mask2former_transformer_decoder.py:479-489: the attention mask samples
+//     the mask logits at 4 h w pixels), bit for bit, without the map.  A value outside [0, P) is clamped by the kernel (no out-of-bounds read); callers
+//     validate their plan once.
+//   weight_image_stride (bytes, % 16) / bias_image_stride (elements): 0 = one weight image and bias for every image, as above; otherwise image b reads
+//     weight_packed + b * weight_image_stride and bias + b * bias_image_stride -- the composed operand of rba_compose_query_operand_f16x2, with which
+//     out [B][N = Q][P] IS einsum("bqc,bchw->bqhw", mask_embed, mask_features(y)) (:479 after pixel_decoder/msdeformattn.py:362).
+// out [B][N][R]; only N channel planes are written (N need not be a multiple of 128).  P % 128 == 0, R % 128 == 0, P K < 2^30.
+extern "C" int rba_split_linear_nchw_out_gn_rows_f16x3_f32(const float* x, const float* mr, const float* gamma, const float* beta, int G, int relu,
+                                                           const void* weight_packed, int64_t weight_image_stride, const float* bias, int bias_image_stride,
+                                                           const int32_t* row_index, float* out, int B, int P, int R, int N, int K, void* stream) {
+  RBA_CHECK_ARG(B >= 0 && N >= 1 && P >= 1 && R >= 1 && G >= 1 && (K % G) == 0 && ((K / G) % 4) == 0);
+  RBA_CHECK_ARG(weight_image_stride >= 0 && (weight_image_stride % 16) == 0 && bias_image_stride >= 0 && (row_index || R == P));
+  const int64_t M = (int64_t)B * R;
+  RBA_GEMM_PROLOGUE(M, K, x && mr && gamma && beta && weight_packed && out && (P % 128) == 0 && (R % 128) == 0 && (int64_t)P * K < (int64_t)1 << 30, x,
+                    weight_packed, out, gamma, beta);
+  H3Args a{x, reinterpret_cast<const u32x4_t*>(weight_packed), bias, out, M, N, K, (hipStream_t)stream};
+  a.rows_per_image = R;
+  a.gn = GnFold{mr, gamma, beta, G, K / G, relu ? 1 : 0};
+  a.rw = H3Rows{row_index, P, bias_image_stride, weight_image_stride};
+  const bool per_image = weight_image_stride != 0 || bias_image_stride != 0, wide = h3_wide(M, N);
+  constexpr unsigned F = H3_NCHW | H3_GNF;
+  if (row_index && per_image) return rba_gemm_status(wide ? launch_h3l<0, 4, F | H3_ROWIDX | H3_PERIMG>(a) : launch_h3l<0, 2, F | H3_ROWIDX | H3_PERIMG>(a));
+  if (row_index) return rba_gemm_status(wide ? launch_h3l<0, 4, F | H3_ROWIDX>(a) : launch_h3l<0, 2, F | H3_ROWIDX>(a));
+  if (per_image) return rba_gemm_status(wide ? launch_h3l<0, 4, F | H3_PERIMG>(a) : launch_h3l<0, 2, F | H3_PERIMG>(a));
+  return rba_gemm_status(wide ? launch_h3l<0, 4, F>(a) : launch_h3l<0, 2, F>(a));
+}

@@ -252,11 +252,13 @@ enum : unsigned {
   H3_OCC1 = 1u << 9,    // h3p: one workgroup per CU, activations prefetched two blocks ahead (OCC = 1; every other form: OCC = 2)
   H3_KS2 = 1u << 10,    // h3p: eight waves, the second four walk the odd k blocks (KS = 2)
   H3_RS2 = 1u << 11,    // h3p: eight waves, 256 x 128 tile over one weight ring (RS = 2)
+  H3_ROWIDX = 1u << 12, // h3l (with H3_NCHW | H3_GNF): A rows gathered through a per-image row index (H3Rows)
+  H3_PERIMG = 1u << 13, // h3l (with H3_NCHW | H3_GNF): every image contracts with its own weight planes and bias (H3Rows)
   H3_PROBE_SHIFT = 16,  // bits 16 ..: the PROBE field (ablation builds of the tune library and the knobs build; results wrong)
 };
 constexpr unsigned h3_probe(int p) { return (unsigned)p << H3_PROBE_SHIFT; }
 constexpr int h3_probe_of(unsigned form) { return (int)(form >> H3_PROBE_SHIFT); }
-constexpr unsigned H3_FORMS = H3_TIMING | H3_RES, H3L_FORMS = H3_FORMS | H3_GNM | H3_CONV | H3_NCHW | H3_GNF,
+constexpr unsigned H3_FORMS = H3_TIMING | H3_RES, H3L_FORMS = H3_FORMS | H3_GNM | H3_CONV | H3_NCHW | H3_GNF | H3_ROWIDX | H3_PERIMG,
                    H3P_FORMS = H3_FORMS | H3_GNM | H3_PRE | H3_FOUT | H3_CONVP | H3_OCC1 | H3_KS2 | H3_RS2;
 constexpr bool h3_form_within(unsigned form, unsigned allowed) { return (form & ~allowed & ((1u << H3_PROBE_SHIFT) - 1)) == 0; }
 // launch geometry of a form: rows of its tile, threads of its workgroup, workgroups per CU it is compiled for
@@ -433,18 +435,30 @@ struct GnFold {
   const float* beta;
   int G, cpg, relu;
 };
-// Product forms (CT = 4 or 2 each): <ACT>, <0, H3_RES> (K <= 256), <0, H3_CONV>, <0, H3_NCHW>, <0, H3_NCHW | H3_GNF> (split_linear_gnf.hip) and <0, 4, H3_GNM>;
-// H3_TIMING and every PROBE: tune library only.
+// ROWIDX / PERIMG (with NCHW | GNF: the mask heads of the masked decoder on the deferred mask-feature operand, docs/kernels/K4.md).  ROWIDX: output row r of
+// image b is source row idx[b][r] of that image's P rows (clamped into [0, P): never read out of bounds) -- the launch covers M = B R output rows, and
+// `rows_per_image` is R, the OUTPUT rows per image (R % 128 == 0: a tile lies inside one image; it indexes mr and strides the channel-major output).  PERIMG: image
+// b reads its weight planes `wstride` bytes and its bias `bstride` elements after image b - 1's.  Per output element the k loop is the plain form's: bit-identical.
+struct H3Rows {
+  const int* idx;      // [B][R] row numbers inside the image (ROWIDX)
+  int P;               // source rows per image (ROWIDX)
+  int bstride;         // elements between per-image biases (PERIMG)
+  int64_t wstride;     // bytes between per-image packed planes (PERIMG)
+};
+// Product forms (CT = 4 or 2 each): <ACT>, <0, H3_RES> (K <= 256), <0, H3_CONV>, <0, H3_NCHW>, <0, H3_NCHW | H3_GNF> alone and with H3_ROWIDX, H3_PERIMG or both
+// (split_linear_gnf.hip) and <0, 4, H3_GNM>; H3_TIMING and every PROBE: tune library only.
 template <int ACT, int CT, unsigned FORM = 0>
 __global__ __launch_bounds__(256, 2) void split_linear_h3l_kernel(const float* __restrict__ A, const u32x4_t* __restrict__ Wp,
                                                                  const float* __restrict__ bias, float* C, int M, int N,
                                                                  int K, int MT, int NT, unsigned long long* dbg = nullptr,
                                                                  ConvShape cs = ConvShape{0, 0, 0}, const float* R = nullptr, int rows_per_image = 0,
                                                                  GnFold gn = GnFold{nullptr, nullptr, nullptr, 1, 1, 0},
-                                                                 GnMoments gm = GnMoments{nullptr, 1, 1, 128}) {
-  static_assert(h3_form_within(FORM, H3L_FORMS), "split_linear_h3l_kernel: H3_TIMING, H3_RES, H3_GNM, H3_CONV, H3_NCHW, H3_GNF, h3_probe()");
+                                                                 GnMoments gm = GnMoments{nullptr, 1, 1, 128}, H3Rows rw = H3Rows{nullptr, 0, 0, 0}) {
+  static_assert(h3_form_within(FORM, H3L_FORMS), "split_linear_h3l_kernel: H3_TIMING, H3_RES, H3_GNM, H3_CONV, H3_NCHW, H3_GNF, H3_ROWIDX, H3_PERIMG, h3_probe()");
   constexpr int PROBE = h3_probe_of(FORM);
   constexpr bool TIMING = FORM & H3_TIMING, CONV = FORM & H3_CONV, RES = FORM & H3_RES, NCHW = FORM & H3_NCHW, GNF = FORM & H3_GNF, GNM = FORM & H3_GNM;
+  constexpr bool ROWIDX = FORM & H3_ROWIDX, PERIMG = FORM & H3_PERIMG;
+  static_assert(!(ROWIDX || PERIMG) || (NCHW && GNF && !CONV && !RES && !GNM), "H3_ROWIDX / H3_PERIMG: forms of the GroupNorm-folded channel-major projection");
   unsigned long long tm[4];
   if (TIMING) tm[0] = wall_clock64();
   constexpr int BM = 128, BN = 32 * CT;
@@ -468,13 +482,18 @@ __global__ __launch_bounds__(256, 2) void split_linear_h3l_kernel(const float* _
 
   constexpr int QSTEP = (CT == 4) ? 256 : 512;
   const char* wbase = reinterpret_cast<const char*>(Wp + (int64_t)(n0 >> 7) * S16 * 512 + (n0 & 127) * 2);
+  const int img = (ROWIDX || PERIMG) ? m0 / rows_per_image : 0;                      // (uniform: the tile lies inside one image)
+  if (PERIMG) {
+    wbase += (int64_t)img * rw.wstride;
+    if (bias) bias += (int64_t)img * rw.bstride;
+  }
   uint32_t woff;
   {
     const int g = tid / SUBW, rem = tid - g * SUBW, p = rem / (2 * BN), rr = rem - p * (2 * BN);
     woff = (uint32_t)(g * 512 + p * 256 + rr) * 16u;
   }
   // activation copy: unit u = tid + 256 q -> row (tid >> 3) + 32 q, chunk tid & 7
-  const char* xbase = reinterpret_cast<const char*>(CONV ? A : A + (int64_t)m0 * K);
+  const char* xbase = reinterpret_cast<const char*>(CONV ? A : ROWIDX ? A + (int64_t)img * rw.P * K : A + (int64_t)m0 * K);
   uint32_t xoff[4];
   int py[4], px[4];                                                                // CONV: the row's pixel (y, x)
 #pragma unroll
@@ -486,6 +505,10 @@ __global__ __launch_bounds__(256, 2) void split_linear_h3l_kernel(const float* _
       py[q] = pix / cs.W;
       px[q] = pix - py[q] * cs.W;
       xoff[q] = ((uint32_t)r * (uint32_t)cs.Cin + 4u * (tid & 7)) * 4u;
+    } else if (ROWIDX) {
+      int s = rw.idx[r];
+      s = s < 0 ? 0 : (s < rw.P ? s : rw.P - 1);
+      xoff[q] = ((uint32_t)s * (uint32_t)K + 4u * (tid & 7)) * 4u;
     } else {
       xoff[q] = ((uint32_t)(r - m0) * (uint32_t)K + 4u * (tid & 7)) * 4u;
     }
@@ -1022,6 +1045,7 @@ struct H3Args {
   GnFold gn = GnFold{nullptr, nullptr, nullptr, 1, 1, 0};  // H3_GNF
   GnMoments gm = GnMoments{nullptr, 1, 1, 128};            // H3_GNM
   int stagger = 0;                                         // h3p, two workgroups per CU: see the kernel
+  H3Rows rw = H3Rows{nullptr, 0, 0, 0};                    // H3_ROWIDX, H3_PERIMG
 };
 
 // MT x NT tiles of rows x cols cover M x N; false where that grid does not fit a launch (2^31 workgroups or more)
@@ -1046,7 +1070,7 @@ int launch_h3l(const H3Args& a) {
   int MT, NT;
   if (!h3_grid(a, 128, 32 * CT, MT, NT)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL((split_linear_h3l_kernel<ACT, CT, FORM>), dim3((unsigned)MT * NT), dim3(256), 0, a.stream, reinterpret_cast<const float*>(a.x), a.wp, a.bias,
-                     reinterpret_cast<float*>(a.out), (int)a.M, a.N, a.K, MT, NT, a.dbg, a.cs, a.res, a.rows_per_image, a.gn, a.gm);
+                     reinterpret_cast<float*>(a.out), (int)a.M, a.N, a.K, MT, NT, a.dbg, a.cs, a.res, a.rows_per_image, a.gn, a.gm, a.rw);
   return 0;
 }
 

@@ -5,7 +5,8 @@ from types import SimpleNamespace
 
 import torch
 
-# everything a captured forward of MaskFormer depends on beside the pixels (MaskFormer._graph_key)
+# everything a captured forward of MaskFormer depends on beside the pixels (MaskFormer._graph_key); `sparse_intermediate_heads` is the pair of switches the mask
+# heads run by: (predictor.sparse_intermediate_heads, ops.COMPOSED_MASK_HEAD)
 GraphKey = namedtuple("GraphKey", "shape dtype device stream return_argmax score fused_upsample fused_front_end split_mode split_activations tiles_min "
                                   "mlp_fused_min_rows concurrent_streams swin_attn_fused sparse_intermediate_heads weights")
 

@@ -27,5 +27,8 @@ class MaskFormerHead(nn.Module):
         return self.layers(features, mask)
 
     def layers(self, features, mask=None):
-        mask_features, _, multi_scale_features = self.pixel_decoder.forward_features(features)
+        # a predictor that takes the deferred mask-feature operand decides itself whether the 1/4-resolution map is ever written (docs/kernels/K4.md)
+        defer = bool(getattr(self.predictor, "takes_deferred_mask_features", False))
+        mask_features, _, multi_scale_features = (self.pixel_decoder.forward_features(features, defer_mask_features=True) if defer
+                                                  else self.pixel_decoder.forward_features(features))
         return self.predictor(multi_scale_features, mask_features, mask)

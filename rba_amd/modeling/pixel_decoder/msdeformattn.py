@@ -18,6 +18,53 @@ from .ops.ms_deform_attn import MSDeformAttn
 FOLD_MASK_FEATURE_NORM = os.environ.get("RBA_MF_GN_FOLD", "1") != "0"
 
 
+class DeferredMaskFeatures:
+    """The mask-feature map `mask_features(layer_1(y))` (reference :357-362) NOT yet computed: the raw rows of the last 3 x 3 convolution `prev` [B*P, d], their
+    GroupNorm statistics `mr` [B, G, 2] and affine, the packed planes and bias of the 1 x 1 convolution, and (h, w).  The masked decoder either asks for the tensor
+    (`materialize`: the launch the pixel decoder would have made, bit for bit) or -- docs/kernels/K4.md -- never builds it: `gather` projects only the rows an
+    attention mask samples, `contract` folds the final einsum("bqc,bchw->bqhw") into the projection."""
+
+    def __init__(self, prev, mr, norm, conv, planes, hw, num_groups=32, relu=True):
+        self.prev, self.mr, self.norm, self.conv, self.planes, self.hw = prev, mr, norm, conv, planes, hw
+        self.num_groups, self.relu = num_groups, relu
+        self.batch = mr.shape[0]
+        self._tensor = None
+
+    @property
+    def shape(self):
+        return torch.Size((self.batch, self.conv.weight.shape[0]) + tuple(self.hw))
+
+    @property
+    def device(self):
+        return self.prev.device
+
+    @property
+    def rows_per_image(self):
+        return self.hw[0] * self.hw[1]
+
+    def _project(self, planes, bias, N, rows=None):
+        return ops.split_linear_nchw_out_gn_rows(self.prev, self.mr, self.norm.weight, self.norm.bias, self.num_groups, self.relu, planes, bias,
+                                                 self.rows_per_image, out_features=N, rows=rows)
+
+    def materialize(self):
+        """-> mask_features [B, md, h, w], once"""
+        if self._tensor is None:
+            md = self.conv.weight.shape[0]
+            self._tensor = ops.split_linear_nchw_out_gn(self.prev, self.mr, self.norm.weight, self.norm.bias, self.num_groups, self.relu, self.planes,
+                                                        self.conv.bias, self.rows_per_image, out_features=md).view(self.shape)
+        return self._tensor
+
+    def gather(self, rows):
+        """rows: ops.RowIndex [B, R] -> mask_features.flatten(2)[:, :, rows] [B, md, R], the very bits, from a projection of those rows alone"""
+        return self._project(self.planes, self.conv.bias, self.conv.weight.shape[0], rows)
+
+    def contract(self, embed):
+        """embed [B, Q, md] -> einsum("bqc,bchw->bqhw", embed, mask_features) [B, Q, h, w]: the pixels contract with embed[b] @ W directly"""
+        w = self.conv.weight
+        planes, bias_q = ops.compose_query_operand(embed, w.detach().view(w.shape[0], -1), self.conv.bias)
+        return self._project(planes, bias_q, embed.shape[1]).view((self.batch, embed.shape[1]) + tuple(self.hw))
+
+
 class _LinearView:
     """A 1x1 convolution's parameters seen as an nn.Linear (weight [N,C], bias) for ops.linear."""
 
@@ -202,7 +249,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         need = set(self.transformer_in_features) | set(self.in_features[:self.num_fpn_levels])
         return all(self._tokens(features[f]) is not None and features[f].shape[1] % 32 == 0 for f in need)
 
-    def _forward_features_channels_last(self, features):
+    def _forward_features_channels_last(self, features, defer_mask_features=False):
         srcs, pos, tks = [], [], []
         for idx, f in enumerate(self.transformer_in_features[::-1]):
             x = features[f]
@@ -277,8 +324,9 @@ class MSDeformAttnPixelDecoder(nn.Module):
             # round 4: the last level's GroupNorm + ReLU feeds only the mask-feature projection (:357-362) -- applied inside that kernel's loads, the
             # normalised 1/4-resolution map (134 MB at 1024 x 2048) is never written or read back
             mr = prev_norm[0] if prev_norm[0] is not None else ops.group_norm_nhwc_stats(prev, 32, prev_norm[1].eps)
-            mf = ops.split_linear_nchw_out_gn(prev.view(B * ph * pw, d), mr, prev_norm[1].weight, prev_norm[1].bias, 32, True, planes,
-                                              self.mask_features.bias, ph * pw, out_features=mfw.shape[0]).view(B, mfw.shape[0], ph, pw)
+            mf = DeferredMaskFeatures(prev.view(B * ph * pw, d), mr, prev_norm[1], self.mask_features, planes, (ph, pw), num_groups=32, relu=True)
+            if not defer_mask_features:                        # (otherwise the masked decoder decides whether the map is ever written)
+                mf = mf.materialize()                          # the one launch site of the folded projection
             return mf, outs[0], outs[:self.maskformer_num_feature_levels]
         if prev_norm is not None:                              # the last level feeds the mask-feature projection: normalised here
             prev = ops.group_norm_nhwc(prev, 32, prev_norm[1].weight, prev_norm[1].bias, prev_norm[1].eps, relu=True)
@@ -286,10 +334,11 @@ class MSDeformAttnPixelDecoder(nn.Module):
                                        out_features=mfw.shape[0]).view(B, mfw.shape[0], ph, pw)
         return mf, outs[0], outs[:self.maskformer_num_feature_levels]
 
-    def forward_features(self, features):
-        """-> (mask_features [B,md,H/4,W/4], out[0], multi_scale_features) (msdeformattn.py:323-367)."""
+    def forward_features(self, features, defer_mask_features=False):
+        """-> (mask_features [B,md,H/4,W/4], out[0], multi_scale_features) (msdeformattn.py:323-367).  ``defer_mask_features`` (the head passes it for a
+        predictor that takes one): mask_features may come back as a DeferredMaskFeatures instead -- only where the GroupNorm-folded projection applies."""
         if self.num_fpn_levels > 0 and self._channels_last_ok(features):
-            return self._forward_features_channels_last(features)
+            return self._forward_features_channels_last(features, defer_mask_features)
         srcs, pos = [], []
         for idx, f in enumerate(self.transformer_in_features[::-1]):
             x = features[f].float().contiguous()                       # (channels-last views from Swin are copied to NCHW here)

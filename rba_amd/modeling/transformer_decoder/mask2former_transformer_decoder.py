@@ -18,6 +18,7 @@ from torch.autograd.function import once_differentiable
 from ... import ops
 from ...lru import ShapeCache, derived, source_key
 from ...registry import TRANSFORMER_DECODER_REGISTRY
+from ..pixel_decoder.msdeformattn import DeferredMaskFeatures
 from .position_encoding import PositionEmbeddingSine
 
 
@@ -244,6 +245,8 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
     the parameters say -- the inference path runs, which builds no autograd graph."""
 
     differentiable_heads = False
+    # forward() accepts the pixel decoder's DeferredMaskFeatures in place of the mask-feature tensor (MaskFormerHead asks for one when this is set)
+    takes_deferred_mask_features = True
 
     def __init__(self, arch):
         super().__init__()
@@ -269,6 +272,7 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         self.sparse_intermediate_heads = True
         self.cache_initial_heads = True          # the heads of the un-decoded queries are constants of the checkpoint (_initial_query_side)
         self._plan_cache = ShapeCache(8)
+        self._row_cache = ShapeCache(8)          # _row_plan: the sparse plans as validated row indices of the gathered projection
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         # v1 checkpoints call query_feat "static_query" (reference :237-258)
@@ -296,6 +300,39 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
 
         plan = self._plan_cache.get(key, build)
         return None if plan is False else plan
+
+    def _row_plan(self, feat_hw, target_hw, device, B):
+        """_sparse_plan as the validated row index [B, 4 h w] of the gathered projection (ops.row_index), or None: no sparse plan for the level, 4 h w not a
+        multiple of 128, or the entry is not cached yet and the stream is capturing (validation reads the values back: never inside a capture)."""
+        key = (tuple(feat_hw), tuple(target_hw), device, B)
+        if key not in self._row_cache and torch.cuda.is_current_stream_capturing():
+            return None
+
+        def build():
+            plan = self._sparse_plan(feat_hw, target_hw, device)
+            if plan is None or plan.numel() % 128:
+                return False
+            rows = ops.row_index(plan.reshape(1, -1).expand(B, -1), feat_hw[0] * feat_hw[1])
+            torch.cuda.current_stream(device).synchronize()          # once per shape: forwards on OTHER streams read the index without an event
+            return rows
+
+        rows = self._row_cache.get(key, build)
+        return None if rows is False else rows
+
+    def _composed_mask_heads(self, mask_features, size_list):
+        """The selection rule of docs/kernels/K4.md: True when this forward never needs the mask-feature map -- every intermediate head call is a sparse one
+        that can project its own rows, and the last call contracts the pixels with the composed operand.  (Its grad-mode clause is forward()'s: a forward with
+        differentiable heads materialises the map before it gets here.)"""
+        if not (ops.COMPOSED_MASK_HEAD and ops.SPLIT_MODE == "f16x3" and self.sparse_intermediate_heads and not self.ood_prediction):
+            return False
+        md = mask_features.shape[1]
+        if self.num_queries > 128 or md > 256 or md % 4 or mask_features.rows_per_image * mask_features.prev.shape[1] >= 1 << 30:
+            return False                                              # (the contracts of ops.compose_query_operand / split_linear_nchw_out_gn_rows)
+        levels = {size_list[i % self.num_feature_levels] for i in range(self.num_layers)}
+        rows = [self._row_plan(mask_features.shape[-2:], lvl, mask_features.device, mask_features.shape[0]) for lvl in sorted(levels)]
+        if any(r is None for r in rows):
+            return False
+        return ops.composed_mask_head_pays(mask_features.rows_per_image, sum(r.data.shape[1] for r in rows))
 
     def _query_side_heads(self, output):
         """decoder_norm -> class_embed, mask_embed MLP on the query tensor [B,Q,C] (reference :473-476): (class logits [B,Q,K+1], mask embedding [B,Q,md])"""
@@ -358,12 +395,20 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             lvl = tuple(attn_mask_target_size)
             gathered = {} if gathered is None else gathered    # per-call dict owned by forward(): the module stays re-entrant
             if lvl not in gathered:                   # mask_features is the same tensor for every layer: gather once per level
-                gathered[lvl] = mask_features.flatten(2).index_select(2, plan.reshape(-1)).contiguous()   # [B,C,4hw]
+                if isinstance(mask_features, DeferredMaskFeatures):          # the same columns, projected from their own rows: the map is never written
+                    gathered[lvl] = mask_features.gather(self._row_plan(mask_features.shape[-2:], lvl, mask_features.device, B))
+                else:
+                    gathered[lvl] = mask_features.flatten(2).index_select(2, plan.reshape(-1)).contiguous()   # [B,C,4hw]
             cols = gathered[lvl]
             v = ops.mask_logits(mask_embed, cols).view(B, -1, 4, plan.shape[1])
             # = 0.5 * (0.5 * v0 + 0.5 * v1) + 0.5 * (0.5 * v2 + 0.5 * v3), the bilinear sample at the centre of a 2 x 2 cell: scaling by a power
             # of two is exact, so the factors can be collected without changing a bit -- ((v0 + v1) + (v2 + v3)) * 0.25 in one launch
             return outputs_class, None, ops.quad_mean(v)
+        if isinstance(mask_features, DeferredMaskFeatures):
+            if need_attn_mask:                                              # (not reached under _composed_mask_heads' rule: a dense intermediate call wants the map)
+                mask_features = mask_features.materialize()
+            else:
+                return outputs_class, mask_features.contract(mask_embed), None
         outputs_mask = ops.mask_logits(mask_embed, mask_features)
         attn_logits = None
         if need_attn_mask:
@@ -381,7 +426,11 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         (reference :398-470).  With ``differentiable_heads`` and grad mode on, everything but the last head call runs under no_grad."""
         assert len(x) == self.num_feature_levels
         del mask
-        frozen = torch.no_grad if self.differentiable_heads and torch.is_grad_enabled() else contextlib.nullcontext
+        differentiable = self.differentiable_heads and torch.is_grad_enabled()
+        frozen = torch.no_grad if differentiable else contextlib.nullcontext
+        if differentiable and isinstance(mask_features, DeferredMaskFeatures):
+            # decided HERE: inside frozen() grad mode reads off.  The differentiable last call wants the map (MaskLogitsFunction), as before
+            mask_features = mask_features.materialize()
         with frozen():
             output, mask_features, side, predictions_class, predictions_mask = self._decode(x, mask_features)
         cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side)
@@ -413,7 +462,10 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             output, side0 = first                                     # constants of the checkpoint (never written: every layer returns new tensors)
         else:
             output, side0 = self.query_feat.weight[None].expand(B, -1, -1).contiguous(), None
-        mask_features = mask_features.contiguous()
+        if isinstance(mask_features, DeferredMaskFeatures) and not self._composed_mask_heads(mask_features, size_list):
+            mask_features = mask_features.materialize()               # today's path from here on, bit for bit
+        if not isinstance(mask_features, DeferredMaskFeatures):
+            mask_features = mask_features.contiguous()
         predictions_class, predictions_mask = [], []
         if self.num_layers == 0:
             return output, mask_features, side0, predictions_class, predictions_mask

@@ -1188,6 +1188,96 @@ def split_linear_nchw_out_gn(x, mr, weight, bias_gn, num_groups, relu, planes, b
     return out
 
 
+COMPOSED_MASK_HEAD = os.environ.get("RBA_COMPOSED_MASK_HEAD", "1") != "0"    # A/B switch (tools): 0 = the masked decoder always materialises the mask-feature map
+
+
+class RowIndex:
+    """A validated row index of split_linear_nchw_out_gn_rows: ``data`` int32 [B, R] with every value inside [0, rows_per_image).  Built by ``row_index`` (which
+    reads the values back once: build it where plans are cached, never inside a graph capture); the launch wrapper takes nothing else, so it never has to look."""
+    __slots__ = ("data", "rows_per_image")
+
+    def __init__(self, data, rows_per_image):
+        self.data, self.rows_per_image = data, rows_per_image
+
+
+def row_index(idx, rows_per_image):
+    """idx: integer tensor [B, R] of row numbers inside an image of `rows_per_image` rows -> RowIndex (int32, contiguous).  Refuses any other dtype or shape and
+    any value outside [0, rows_per_image)."""
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 2 or idx.numel() == 0:
+        raise RbaHipError("row_index needs a HIP int32 / int64 tensor [B, R]")
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= rows_per_image:
+        raise RbaHipError(f"row_index: values must lie in [0, {rows_per_image}), got [{lo}, {hi}]")
+    return RowIndex(idx.to(torch.int32).contiguous(), int(rows_per_image))
+
+
+def _image_planes(planes, K, out_features, B):
+    """f16x3 planes shared by every image ([nt, K/16, 2, 128, 2, 8], `_packed`'s contract) or one image each ([B, nt, K/16, 2, 128, 2, 8]) -> (N, byte stride)."""
+    if planes.dim() != 7:
+        return _packed(planes, K, out_features, bf16x6=False)[0], 0
+    _chk(planes, "planes", dtype=torch.float16, dim=7)
+    if planes.shape[0] != B:
+        raise RbaHipError(f"per-image planes must be [B = {B}, ...], got {tuple(planes.shape)}")
+    return _packed(planes[0], K, out_features, bf16x6=False)[0], planes.stride(0) * 2
+
+
+@_hip_op
+def split_linear_nchw_out_gn_rows(x, mr, weight, bias_gn, num_groups, relu, planes, bias, rows_per_image, out_features=None, rows=None):
+    """split_linear_nchw_out_gn on selected rows and / or with per-image operands (the mask heads on the deferred mask-feature operand, docs/kernels/K4.md):
+    rows = RowIndex [B, R] -> out [B, N, R], bit-identical to split_linear_nchw_out_gn(...)[:, :, rows] (None: every row, R = P); planes [B, nt, ...] and bias [B, N]
+    give image b its own weight image and bias (compose_query_operand).  P % 128 == 0 and R % 128 == 0."""
+    _chk(x, "x", dim=2)
+    _chk(mr, "mr", dim=3)
+    M, K = x.shape
+    P = int(rows_per_image)
+    if P < 1 or M % P or planes.dtype != torch.float16 or not split_linear_nchw_out_takes_gn(planes, P, K, num_groups) or P * K >= 1 << 30:
+        raise RbaHipError("split_linear_nchw_out_gn_rows needs x [B*P, K], float16 planes, P % 128 == 0, (K / G) % 4 == 0 and P * K < 2^30")
+    B = M // P
+    N, wstride = _image_planes(planes, K, out_features, B)
+    if tuple(mr.shape) != (B, num_groups, 2):
+        raise RbaHipError("mr must be [B, G, 2]")
+    _vec(weight, "weight", K)
+    _vec(bias_gn, "bias_gn", K)
+    bstride = 0
+    if bias is not None and bias.dim() == 2:
+        _shaped(bias, "bias", (B, N))
+        bstride = N
+    else:
+        _vec(bias, "bias", N, optional=True)
+    R = P
+    if rows is not None:
+        if not isinstance(rows, RowIndex) or rows.rows_per_image != P or rows.data.shape[0] != B or rows.data.shape[1] % 128 or rows.data.device != x.device:
+            raise RbaHipError("rows must be ops.row_index(idx [B, R], rows_per_image) for this x, with R % 128 == 0")
+        R = rows.data.shape[1]
+    out = torch.empty((B, N, R), dtype=torch.float32, device=x.device)
+    _launch("rba_split_linear_nchw_out_gn_rows_f16x3_f32", _p(x), _p(mr), _p(weight), _p(bias_gn), int(num_groups), int(bool(relu)), _p(planes), wstride, _p(bias),
+            bstride, _p(None if rows is None else rows.data), _p(out), B, P, R, N, K)
+    return out
+
+
+@_hip_op
+def compose_query_operand(embed, weight, bias):
+    """embed [B, Q, C] (the mask embeddings), weight [C, K] and bias [C] | None of the mask-feature 1 x 1 convolution -> (planes [B, 1, K/16, 2, 128, 2, 8] float16:
+    split_weight(embed[b] @ weight) per image, bias_q [B, Q] = embed[b] @ bias) in one launch; fp32 FMAs in a fixed order.  Q <= 128, C <= 256, C % 4 == 0, K % 32 == 0."""
+    _chk(embed, "embed", dim=3)
+    _chk(weight, "weight", dim=2)
+    B, Q, C = embed.shape
+    K = weight.shape[1]
+    if weight.shape[0] != C or not (1 <= Q <= 128 and 4 <= C <= 256 and C % 4 == 0 and K >= 32 and K % 32 == 0):
+        raise RbaHipError("compose_query_operand needs embed [B, Q <= 128, C <= 256] (C % 4 == 0) and weight [C, K] with K % 32 == 0")
+    _vec(bias, "bias", C, optional=True)
+    planes = torch.empty((B, 1, K // 16, 2, 128, 2, 8), dtype=torch.float16, device=embed.device)
+    bias_q = torch.empty((B, Q), dtype=torch.float32, device=embed.device)
+    _launch("rba_compose_query_operand_f16x2", _p(embed), _p(weight), _p(bias), _p(planes), _p(bias_q), B, Q, C, K)
+    return planes, bias_q
+
+
+def composed_mask_head_pays(rows_per_image, sparse_rows):
+    """The shape half of the masked decoder's selection rule (docs/kernels/K4.md): projecting the attention masks' gathered rows (`sparse_rows`: summed over the
+    levels the layers use) instead of the whole map pays while they are at most half the map's rows."""
+    return 2 * sparse_rows <= rows_per_image
+
+
 @_hip_op
 def conv3x3_weight(weight, mode=None):
     """conv weight [N, C, 3, 3] -> split_weight (form `mode`, default ops.SPLIT_MODE) of the implicit-GEMM matrix [N, 9 C],
