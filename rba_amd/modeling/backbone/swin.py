@@ -73,68 +73,78 @@ class SwinTransformerBlock(nn.Module):
 
     def forward(self, x, H, W, pending=None):
         """x [B, H*W, C] residual stream; ``pending`` = (t, bias) not yet added to it (the previous block's fc2 output).
-        Returns (x, pending) with this block's fc2 output pending (reference dataflow: swin.py:235-295).  The residual
-        adds and projection biases are folded into the fused add+LayerNorm kernel."""
-        a = self.attn
-        t, tb = pending if pending is not None else (None, None)
-        M, C = x.numel() // x.shape[-1], x.shape[-1]
-        if x.is_cuda and x.dim() == 3 and ops.swin_attn_block_ok(C, self.num_heads, self.window_size):
+        Returns (x, pending): this block's fc2 output is pending wherever no GEMM epilogue added it (reference dataflow: swin.py:235-295)."""
+        M, C, hidden = x.numel() // x.shape[-1], x.shape[-1], self.mlp.fc2.in_features
+        attn, mlp = self._select(x, pending, M, C, hidden)
+        x, y = self._attention(attn, mlp, x, H, W, pending, M, C)
+        return self._mlp(mlp, x, y, M, C, hidden)
+
+    # The launch paths of a block, each written once below.  Attention half: A1 = K7 with proj (one kernel), A2 = K7 without proj + the proj GEMM,
+    # A3 = LayerNorm, qkv GEMM, K5, proj GEMM.  MLP half: M1 / M5 = the one-kernel MLP with / without norm2 inside, M2 / M4 = fc1 -> fc2 with the residual in
+    # fc2's epilogue, norm2 from K7 / from a LayerNorm launch, M3 / M6 = fc1 -> fc2 left pending, norm2 from K7 / from the add+LayerNorm that also adds proj.
+    # _select -> (attention path, MLP path), both chosen before either launches: whether K7 (A1) computes norm2 is the MLP path's decision.
+    # _attention -> (x, y): y = norm2(x) from K7 (in front of M2, M3), proj's output not yet added to x (M6), None where the MLP half normalises a complete x itself.
+    # _mlp -> (x, pending): x + fc2(GELU(fc1(norm2(x)))), the sum made here (pending None) or left to the next add+LayerNorm (M3, M6).
+    def _select(self, x, pending, M, C, hidden):
+        if x.is_cuda and x.dim() == 3:
+            if ops.swin_attn_block_ok(C, self.num_heads, self.window_size):
+                return "A1", "M1" if ops.mlp_fused_ok(M, C, hidden) else "M2" if ops.linear_residual_fused(M, C, hidden) else "M3"
+            # a term the previous block left pending refuses A2 (A1 folds it with tensor adds)
+            if pending is None and ops.swin_attn_qkv_ok(C, self.num_heads, self.window_size) and ops.linear_residual_fused(M, C, C) and ops.linear_takes_split(M, C, C):
+                return "A2", "M4"
+        if not ops.linear_residual_fused(M, C, C):
+            return "A3", "M6"
+        return "A3", "M5" if ops.mlp_fused_ok(M, C, hidden) else "M4"
+
+    def _attention(self, path, mlp, x, H, W, pending, M, C):
+        a, n1, n2 = self.attn, self.norm1, self.norm2
+        if path == "A1":
             # K7: norm1 -> qkv -> (shifted-)window attention -> proj -> + shortcut -> norm2 in ONE kernel, in place over x
             if pending is not None:
-                x = x + t + tb
-            x = x.contiguous()
+                x = x + pending[0] + pending[1]
             bias_frag = a.gathered_bias()[1]
-            hidden = self.mlp.fc1.out_features
-            n2 = (self.norm2.weight, self.norm2.bias, self.norm2.eps)
-            fused_mlp = ops.mlp_fused_ok(M, C, hidden)               # the one-kernel MLP computes norm2 itself from the residual stream: K7 then writes x only
-            x, y = ops.swin_attn_block(x, (self.norm1.weight, self.norm1.bias, self.norm1.eps), a.block_image(), a.qkv.bias, bias_frag, a.proj.bias, H, W,
-                                       self.window_size, self.shift_size, norm2=None if fused_mlp else n2)
-            if fused_mlp:
-                return ops.mlp_fused_ln(x, n2, self.mlp.fc1, self.mlp.fc2), None
-            if ops.linear_residual_fused(M, C, hidden):
-                y = ops.linear(y, self.mlp.fc1, gelu=True, split_out=ops.linear_takes_split(M, C, hidden))
-                return ops.linear(y, self.mlp.fc2, residual=x), None
-            y = ops.linear(y, self.mlp.fc1, gelu=True)
-            return x, (ops.linear(y, self.mlp.fc2, use_bias=False), self.mlp.fc2.bias)
-        if (x.is_cuda and x.dim() == 3 and pending is None and ops.swin_attn_qkv_ok(C, self.num_heads, self.window_size)
-                and ops.linear_residual_fused(M, C, C) and ops.linear_takes_split(M, C, C)):
+            # the one-kernel MLP (M1) computes norm2 itself from the residual stream: K7 then writes x only
+            return ops.swin_attn_block(x.contiguous(), (n1.weight, n1.bias, n1.eps), a.block_image(), a.qkv.bias, bias_frag, a.proj.bias, H, W,
+                                       self.window_size, self.shift_size, norm2=None if mlp == "M1" else (n2.weight, n2.bias, n2.eps))
+        if path == "A2":
             # K7 without proj (C = 256, Swin-B stage 2): norm1 -> qkv -> window attention in ONE kernel, its output the proj GEMM's split operand; the residual
             # add rides in that GEMM's epilogue as before
             x = x.contiguous()
-            y = ops.swin_attn_qkv(x, (self.norm1.weight, self.norm1.bias, self.norm1.eps), a.block_image(), a.qkv.bias, a.gathered_bias()[1], H, W,
-                                  self.window_size, self.shift_size)
-            x = ops.linear(y, a.proj, residual=x)
-            hidden = self.mlp.fc1.out_features
-            y = ops.add_layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, frag=ops.linear_takes_split(M, hidden, C))[1]
-            y = ops.linear(y, self.mlp.fc1, gelu=True, split_out=ops.linear_takes_split(M, C, hidden))
-            return ops.linear(y, self.mlp.fc2, residual=x), None
-        # where the consumer is the pipelined f16x3 GEMM, the LayerNorm hands its output over already split and in MFMA fragment
+            y = ops.swin_attn_qkv(x, (n1.weight, n1.bias, n1.eps), a.block_image(), a.qkv.bias, a.gathered_bias()[1], H, W, self.window_size, self.shift_size)
+            return ops.linear(y, a.proj, residual=x), None
+        # A3.  Where the consumer is the pipelined f16x3 GEMM, the LayerNorm hands its output over already split and in MFMA fragment
         # order (ops.SplitActivations): one split per element instead of one per column tile, contiguous operand loads
-        x, y = ops.add_layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, t, tb, inplace_sum=True,
-                                  frag=ops.linear_takes_split(M, 3 * C, C))
+        t, tb = pending if pending is not None else (None, None)
+        x, y = ops.add_layer_norm(x, n1.weight, n1.bias, n1.eps, t, tb, inplace_sum=True, frag=ops.linear_takes_split(M, 3 * C, C))
         qkv = ops.linear(y, a.qkv)
         bias, bias_frag = a.gathered_bias()
-        fused = ops.linear_residual_fused(M, C, C)
         y = ops.swin_window_attn(qkv, a.qkv.bias, bias, H, W, self.num_heads, self.window_size, self.shift_size, bias_frag=bias_frag,
-                                 split_out=fused and bias_frag is not None and ops.linear_takes_split(M, C, C) and
+                                 split_out=mlp != "M6" and bias_frag is not None and ops.linear_takes_split(M, C, C) and
                                  ops.swin_window_attn_split_ok(C // self.num_heads, self.window_size))
-        if fused:
-            # the residual adds ride in the GEMM epilogues (x is updated in place), the LayerNorms read one tensor and write one
-            x = ops.linear(y, a.proj, residual=x)
-            hidden = self.mlp.fc1.out_features
-            if ops.mlp_fused_ok(M, C, hidden):
-                # C = 128 (Swin-B stage 1): fc1 + GELU + fc2 + residual in ONE kernel, the 4C-wide hidden tensor never leaves the registers
-                y = ops.add_layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)[1]
-                return ops.mlp_fused(y, self.mlp.fc1, self.mlp.fc2, x), None
+        if mlp == "M6":
+            return x, ops.linear(y, a.proj, use_bias=False)                  # proj bias rides in M6's fused add+LN
+        # the residual adds ride in the GEMM epilogues (x is updated in place), the LayerNorms read one tensor and write one
+        return ops.linear(y, a.proj, residual=x), None
+
+    def _mlp(self, path, x, y, M, C, hidden):
+        fc1, fc2, n2 = self.mlp.fc1, self.mlp.fc2, self.norm2
+        if path == "M1":
+            return ops.mlp_fused_ln(x, (n2.weight, n2.bias, n2.eps), fc1, fc2), None
+        if path == "M5":
+            # C = 128 (Swin-B stage 1): fc1 + GELU + fc2 + residual in ONE kernel, the 4C-wide hidden tensor never leaves the registers
+            y = ops.add_layer_norm(x, n2.weight, n2.bias, n2.eps)[1]
+            return ops.mlp_fused(y, fc1, fc2, x), None
+        if path in ("M2", "M4"):
             # fc2 reads fc1's output as its split operand wherever it runs the pipelined kernel; fc1's own input comes split from
-            # the LayerNorm only where K > 256 (below, the scattered 16-byte stores cost the LayerNorm more than the GEMM gains)
-            y = ops.add_layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, frag=ops.linear_takes_split(M, hidden, C))[1]
-            y = ops.linear(y, self.mlp.fc1, gelu=True, split_out=ops.linear_takes_split(M, C, hidden))
-            return ops.linear(y, self.mlp.fc2, residual=x), None
-        t = ops.linear(y, a.proj, use_bias=False)                        # proj bias rides in the fused add+LN
-        x, y = ops.add_layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, t, a.proj.bias, inplace_sum=True)
-        y = ops.linear(y, self.mlp.fc1, gelu=True)                       # exact GELU in the GEMM epilogue
-        return x, (ops.linear(y, self.mlp.fc2, use_bias=False), self.mlp.fc2.bias)
+            # the LayerNorm only where K > 256 (below, the scattered 16-byte stores cost the LayerNorm more than the GEMM gains), and never from K7 (M2: fp32 y)
+            if path == "M4":
+                y = ops.add_layer_norm(x, n2.weight, n2.bias, n2.eps, frag=ops.linear_takes_split(M, hidden, C))[1]
+            y = ops.linear(y, fc1, gelu=True, split_out=ops.linear_takes_split(M, C, hidden))
+            return ops.linear(y, fc2, residual=x), None
+        if path == "M6":
+            x, y = ops.add_layer_norm(x, n2.weight, n2.bias, n2.eps, y, self.attn.proj.bias, inplace_sum=True)
+        y = ops.linear(y, fc1, gelu=True)                                    # M3, M6: exact GELU in the GEMM epilogue
+        return x, (ops.linear(y, fc2, use_bias=False), fc2.bias)
 
 
 class PatchMerging(nn.Module):

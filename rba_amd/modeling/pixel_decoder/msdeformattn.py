@@ -1,8 +1,6 @@
 """MSDeformAttn pixel decoder, inference only (reference: pixel_decoder/msdeformattn.py:32-367).
 Same parameter names; K2 (deformable attention) and the bilinear FPN top-down sum are HIP kernels, the 1x1 / 3x3
 convolutions and the encoder FFN are this library's split-precision MFMA GEMMs / implicit GEMM (K6, conv3x3.hip) -- no rocBLAS / MIOpen call on any path (round 5)."""
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -13,9 +11,6 @@ from ...lru import ShapeCache, derived, source_key
 from ...registry import SEM_SEG_HEADS_REGISTRY
 from ..transformer_decoder.position_encoding import PositionEmbeddingSine
 from .ops.ms_deform_attn import MSDeformAttn
-
-# tools (A/B runs): RBA_MF_GN_FOLD=0 keeps the last FPN level's GroupNorm + ReLU a separate pass in front of the mask-feature projection
-FOLD_MASK_FEATURE_NORM = os.environ.get("RBA_MF_GN_FOLD", "1") != "0"
 
 
 class DeferredMaskFeatures:
@@ -217,7 +212,6 @@ class MSDeformAttnPixelDecoder(nn.Module):
         self.pe_layer = PositionEmbeddingSine(d // 2, normalize=True)
         self.mask_features = nn.Conv2d(d, a["mask_dim"], kernel_size=1)
         self.num_fpn_levels = num_fpn_levels(a)
-        self.fold_group_norm = os.environ.get("RBA_FOLD_GN", "1") != "0"          # channels-last FPN: GroupNorm "apply" passes folded into the resample kernel (A/B: False)
         for j in range(1, self.num_fpn_levels + 1):
             self.add_module(f"adapter_{j}", ConvNorm(chans[FEATURE_NAMES[j - 1]], d, 1, bias=False, norm=True))
             self.add_module(f"layer_{j}", ConvNorm(d, d, 3, bias=False, norm=True, relu=True))
@@ -249,7 +243,8 @@ class MSDeformAttnPixelDecoder(nn.Module):
         need = set(self.transformer_in_features) | set(self.in_features[:self.num_fpn_levels])
         return all(self._tokens(features[f]) is not None and features[f].shape[1] % 32 == 0 for f in need)
 
-    def _forward_features_channels_last(self, features, defer_mask_features=False):
+    def _encode_channels_last(self, features):
+        """Input projections + encoder on the token layout -> (multi-scale outs, finest encoder level as NHWC [B, h, w, d])"""
         srcs, pos, tks = [], [], []
         for idx, f in enumerate(self.transformer_in_features[::-1]):
             x = features[f]
@@ -264,75 +259,66 @@ class MSDeformAttnPixelDecoder(nn.Module):
         toks = [z.contiguous() for z in torch.split(y, [h * w for h, w in shapes], dim=1)]
         # multi-scale features for the masked decoder: channels-last VIEWS of the token tensors (the decoder reads them as tokens again)
         outs = [z.view(B, h, w, d).permute(0, 3, 1, 2) for z, (h, w) in zip(toks, shapes)]
-        prev, (ph, pw) = toks[-1], shapes[-1]
-        prev_norm = None                                   # (mr [B, G, 2], module) once `prev` is a raw convolution output awaiting GroupNorm + ReLU
-        fold = self.fold_group_norm
-        for idx, f in enumerate(self.in_features[:self.num_fpn_levels][::-1]):
-            j = self.num_fpn_levels - idx
-            x = features[f]
-            h, w = int(x.shape[-2]), int(x.shape[-1])
-            ad, ly = getattr(self, f"adapter_{j}"), getattr(self, f"layer_{j}")
-            tok = self._tokens(x)
-            lat_mr = None
-            if fold and tok.is_contiguous() and ops.linear_emits_gn_moments(B * h * w, d, tok.shape[-1], h * w, 32):
-                # round 4: the lateral convolution's epilogue leaves the GroupNorm moments of its output -- no statistics pass over `lat`
-                lat, lat_mr = ops.linear_gn_stats(tok, _cached_linear_view(ad), 32, ad.norm.eps, h * w, use_bias=False)
-            else:
-                lat = self._conv1x1(tok, ad, use_bias=False)                               # raw lateral convolution [B, h*w, d]
-            split = ops.conv3x3_takes_split(B * h * w, d) and d % 32 == 0
-            yy = ops.SplitActivations.empty((B, h, w, d), prev.device) if split else None
-            if fold:
-                # round 3: both GroupNorms of the top-down step are folded into the resample kernel's loads -- the lateral's (no ReLU) into its
-                # `add` operand, the previous level's (+ ReLU) into its taps: their "apply" passes (268 MB each at 256 x 512) are never run
-                if lat_mr is None:
-                    lat_mr = ops.group_norm_nhwc_stats(lat, 32, ad.norm.eps)
-                ups = []
-                for b in range(B):
-                    xn = None if prev_norm is None else (prev_norm[0][b], prev_norm[1].weight, prev_norm[1].bias, True)
-                    r = ops.resample_bilinear_nhwc_gn(prev[b].view(ph, pw, d), (h, w), lat[b].view(h, w, d), 32, x_norm=xn,
-                                                      add_norm=(lat_mr[b], ad.norm.weight, ad.norm.bias), split_into=yy, image=b)
-                    if not split:
-                        ups.append(r)
-                if not split:
-                    yy = ups[0][None] if B == 1 else torch.stack(ups)
-            else:
-                if prev_norm is not None:
-                    prev = ops.group_norm_nhwc(prev, 32, prev_norm[1].weight, prev_norm[1].bias, prev_norm[1].eps, relu=True)
-                cur = ops.group_norm_nhwc(lat, 32, ad.norm.weight, ad.norm.bias, ad.norm.eps)
-                if split:
-                    # the sum feeds only the 3x3 convolution: written straight as that kernel's split operand (ops.SplitActivations)
-                    for b in range(B):
-                        ops.resample_bilinear_nhwc(prev[b].view(ph, pw, d), (h, w), add=cur[b].view(h, w, d), split_into=yy, image=b)
-                else:
-                    ups = [ops.resample_bilinear_nhwc(prev[b].view(ph, pw, d), (h, w), add=cur[b].view(h, w, d))
-                           for b in range(B)]                                                  # :357-358 fused sum
-                    yy = ups[0][None] if B == 1 else torch.stack(ups)
-            planes = _conv3x3_planes(ly)
-            last = idx == self.num_fpn_levels - 1                  # its GroupNorm is applied below, inside the mask-feature projection
-            if fold and split and ops.conv3x3_emits_gn_moments(B, h, w, d, 32):
-                prev, mr = ops.conv3x3_nhwc_gn_stats(yy, planes, 32, ly.norm.eps, None, out_features=d)     # round 4: statistics from the convolution's epilogue
-                prev_norm = (mr, ly.norm)
-                prev = prev.view(B, h * w, d)
-            else:
-                prev = ops.conv3x3_nhwc(yy, planes, None, out_features=d).view(B, h * w, d)   # raw: its GroupNorm + ReLU is folded into the next consumer
-                prev_norm = (ops.group_norm_nhwc_stats(prev, 32, ly.norm.eps) if fold and not last else None, ly.norm)
-            ph, pw = h, w
+        return outs, toks[-1].view(B, *shapes[-1], d)
+
+    def _top_down_level(self, prev, prev_norm, j, x):
+        """FPN level j (reference :343-360) from the coarser level's `prev` [B, ph, pw, d] and backbone feature x -> (prev, prev_norm) of this level: the RAW
+        output of its 3 x 3 convolution and (mr [B, G, 2] | None, module), the GroupNorm + ReLU its consumer applies (prev_norm None: `prev` is used as it is)."""
+        B, d = prev.shape[0], prev.shape[-1]
+        h, w = int(x.shape[-2]), int(x.shape[-1])
+        ad, ly = getattr(self, f"adapter_{j}"), getattr(self, f"layer_{j}")
+        tok = self._tokens(x)
+        if tok.is_contiguous() and ops.linear_emits_gn_moments(B * h * w, d, tok.shape[-1], h * w, 32):
+            # round 4: the lateral convolution's epilogue leaves the GroupNorm moments of its output -- no statistics pass over `lat`
+            lat, lat_mr = ops.linear_gn_stats(tok, _cached_linear_view(ad), 32, ad.norm.eps, h * w, use_bias=False)
+        else:
+            lat = self._conv1x1(tok, ad, use_bias=False)                               # raw lateral convolution [B, h*w, d]
+            lat_mr = ops.group_norm_nhwc_stats(lat, 32, ad.norm.eps)
+        # the sum feeds only the 3x3 convolution: where that kernel takes one, written straight as its split operand (ops.SplitActivations)
+        split = ops.conv3x3_takes_split(B * h * w, d) and d % 32 == 0
+        yy = ops.SplitActivations.empty((B, h, w, d), prev.device) if split else None
+        # round 3: both GroupNorms of the top-down step are folded into the resample kernel's loads -- the lateral's (no ReLU) into its
+        # `add` operand, the previous level's (+ ReLU) into its taps: their "apply" passes (268 MB each at 256 x 512) are never run
+        ups = []
+        for b in range(B):
+            xn = None if prev_norm is None else (prev_norm[0][b], prev_norm[1].weight, prev_norm[1].bias, True)
+            ups.append(ops.resample_bilinear_nhwc_gn(prev[b], (h, w), lat[b].view(h, w, d), 32, x_norm=xn,
+                                                     add_norm=(lat_mr[b], ad.norm.weight, ad.norm.bias), split_into=yy, image=b))
+        if not split:
+            yy = ups[0][None] if B == 1 else torch.stack(ups)
+        planes = _conv3x3_planes(ly)
+        if split and ops.conv3x3_emits_gn_moments(B, h, w, d, 32):
+            prev, mr = ops.conv3x3_nhwc_gn_stats(yy, planes, 32, ly.norm.eps, None, out_features=d)     # round 4: statistics from the convolution's epilogue
+            return prev, (mr, ly.norm)
+        prev = ops.conv3x3_nhwc(yy, planes, None, out_features=d)
+        # the last level's GroupNorm is applied inside the mask-feature projection, which takes its statistics where it needs them
+        return prev, (ops.group_norm_nhwc_stats(prev.flatten(1, 2), 32, ly.norm.eps) if j > 1 else None, ly.norm)
+
+    def _mask_features(self, prev, prev_norm, defer):
+        """mask_features(ReLU(GroupNorm(prev))) (reference :357-362) of the last level's raw rows -> [B, md, h, w], or a DeferredMaskFeatures"""
+        B, ph, pw, d = prev.shape
+        mr, norm = prev_norm
         mfw = self.mask_features.weight
         planes = derived(self.mask_features, ("mf_planes", ops.SPLIT_MODE), (mfw, self.mask_features.bias),      # per arithmetic form (f16x3 since round 3)
                          lambda: ops.split_weight(mfw.detach().view(mfw.shape[0], -1).contiguous()))
-        if prev_norm is not None and fold and FOLD_MASK_FEATURE_NORM and ops.split_linear_nchw_out_takes_gn(planes, ph * pw, d, 32):
-            # round 4: the last level's GroupNorm + ReLU feeds only the mask-feature projection (:357-362) -- applied inside that kernel's loads, the
+        if ops.split_linear_nchw_out_takes_gn(planes, ph * pw, d, 32):
+            # round 4: the last level's GroupNorm + ReLU feeds only the mask-feature projection -- applied inside that kernel's loads, the
             # normalised 1/4-resolution map (134 MB at 1024 x 2048) is never written or read back
-            mr = prev_norm[0] if prev_norm[0] is not None else ops.group_norm_nhwc_stats(prev, 32, prev_norm[1].eps)
-            mf = DeferredMaskFeatures(prev.view(B * ph * pw, d), mr, prev_norm[1], self.mask_features, planes, (ph, pw), num_groups=32, relu=True)
-            if not defer_mask_features:                        # (otherwise the masked decoder decides whether the map is ever written)
-                mf = mf.materialize()                          # the one launch site of the folded projection
-            return mf, outs[0], outs[:self.maskformer_num_feature_levels]
-        if prev_norm is not None:                              # the last level feeds the mask-feature projection: normalised here
-            prev = ops.group_norm_nhwc(prev, 32, prev_norm[1].weight, prev_norm[1].bias, prev_norm[1].eps, relu=True)
-        mf = ops.split_linear_nchw_out(prev.view(B * ph * pw, d), planes, self.mask_features.bias, ph * pw,
-                                       out_features=mfw.shape[0]).view(B, mfw.shape[0], ph, pw)
-        return mf, outs[0], outs[:self.maskformer_num_feature_levels]
+            if mr is None:
+                mr = ops.group_norm_nhwc_stats(prev.flatten(1, 2), 32, norm.eps)
+            mf = DeferredMaskFeatures(prev.view(B * ph * pw, d), mr, norm, self.mask_features, planes, (ph, pw), num_groups=32, relu=True)
+            # deferred: the masked decoder decides whether the map is ever written; materialize() is the one launch site of the folded projection
+            return mf if defer else mf.materialize()
+        prev = ops.group_norm_nhwc(prev.flatten(1, 2), 32, norm.weight, norm.bias, norm.eps, relu=True)
+        return ops.split_linear_nchw_out(prev.view(B * ph * pw, d), planes, self.mask_features.bias, ph * pw,
+                                         out_features=mfw.shape[0]).view(B, mfw.shape[0], ph, pw)
+
+    def _forward_features_channels_last(self, features, defer_mask_features=False):
+        outs, prev = self._encode_channels_last(features)
+        prev_norm = None
+        for j in range(self.num_fpn_levels, 0, -1):
+            prev, prev_norm = self._top_down_level(prev, prev_norm, j, features[self.in_features[j - 1]])
+        return self._mask_features(prev, prev_norm, defer_mask_features), outs[0], outs[:self.maskformer_num_feature_levels]
 
     def forward_features(self, features, defer_mask_features=False):
         """-> (mask_features [B,md,H/4,W/4], out[0], multi_scale_features) (msdeformattn.py:323-367).  ``defer_mask_features`` (the head passes it for a
