@@ -59,6 +59,16 @@ __device__ __forceinline__ float rba_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
 
+// K3's threshold on an attention-mask logit: blocked iff the reference's `sigmoid(x) < 0.5` (mask2former_transformer_decoder.py:486), as torch evaluates it in
+// fp32 -- true for x <= -1.7881392e-07 (bits 0xb43fffff), false for the next float up (0xb43ffffe) and everything above it: -2^-23, -0.0, denormals, NaN.
+// rba_sigmoid(x) < 0.5f is NOT that predicate near zero (v_exp_f32 and v_rcp_f32 round 1 + e^-x their own way); one compare is, for every fp32 input, and it is
+// cheaper.  tests/test_kernels_gpu.py re-derives the two bit patterns from torch and plants them in all three forms of K3.
+__device__ __forceinline__ bool rba_mask_blocked(float x) {
+  constexpr float boundary = -0x1.7ffffep-23f;
+  static_assert(__builtin_bit_cast(unsigned, boundary) == 0xb43fffffu, "the largest fp32 x with torch.sigmoid(x) < 0.5");
+  return x <= boundary;
+}
+
 // The same sigmoid on two values with the multiply and the add packed (v_pk_mul_f32 / v_pk_add_f32): identical operations per
 // element (x * -log2(e), v_exp_f32, + 1, v_rcp_f32), two VALU issues fewer per pair.
 __device__ __forceinline__ f32x2 rba_sigmoid2(f32x2 x) {

@@ -32,11 +32,11 @@ __global__ __launch_bounds__(256) void masked_xattn_kernel(const float* __restri
   __shared__ float sh_m[4], sh_l[4], sh_acc[4][HD];
 
   const float* mrow = mlog ? mlog + ((int64_t)b * Q + qi) * S : nullptr;
-  // does the row have any un-blocked key?  (blocked iff sigmoid(x) < 0.5)
+  // does the row have any un-blocked key?  (blocked iff sigmoid(x) < 0.5: rba_mask_blocked)
   bool use_mask = false;
   if (mrow) {
     float any = 0.f;
-    for (int s = tid; s < S; s += 256) any = fmaxf(any, rba_sigmoid(mrow[s]) < 0.5f ? 0.f : 1.f);
+    for (int s = tid; s < S; s += 256) any = fmaxf(any, rba_mask_blocked(mrow[s]) ? 0.f : 1.f);
     any = wave_reduce_max(any);
     if (lane == 0) sh_any[wave] = any;
     __syncthreads();
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void masked_xattn_kernel(const float* __restri
   const float* kb = k + (int64_t)b * S * rs + h * HD;
   const float* vb = v + (int64_t)b * S * rs + h * HD;
   for (int s = tid; s < S; s += 256) {
-    if (use_mask && rba_sigmoid(mrow[s]) < 0.5f) continue;
+    if (use_mask && rba_mask_blocked(mrow[s])) continue;
     const float4* kr = reinterpret_cast<const float4*>(kb + s * rs);
     float sc = 0.f;
 #pragma unroll
@@ -126,7 +126,7 @@ constexpr int XC = 144, XNT = 9, XRS = 36;      // keys per chunk, 16-key tiles 
 __global__ __launch_bounds__(256) void xattn_rowflag_kernel(const float* __restrict__ mlog, int* __restrict__ flag, int S) {
   const float* row = mlog + (int64_t)blockIdx.x * S;          // blockIdx.x = b*Q + q
   float any = 0.f;
-  for (int s = threadIdx.x; s < S; s += 256) any = fmaxf(any, rba_sigmoid(row[s]) < 0.5f ? 0.f : 1.f);
+  for (int s = threadIdx.x; s < S; s += 256) any = fmaxf(any, rba_mask_blocked(row[s]) ? 0.f : 1.f);
   any = wave_reduce_max(any);
   __shared__ float sh[4];
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = any;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64 * WAVES) void xattn_partial_mfma_kernel(const fl
 #pragma unroll
     for (int c = 0; c < XNT; ++c) {
       const int k0i = kbase + c * 16 + kk * 4;
-      float mv[4] = {1.f, 1.f, 1.f, 1.f};                    // any value with sigmoid >= 0.5
+      float mv[4] = {1.f, 1.f, 1.f, 1.f};                    // any value that is not blocked
       if (use_mask) {
         if (vec_mask && k0i + 3 < S) {
           const float4 t4 = *reinterpret_cast<const float4*>(mrow + k0i);
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(64 * WAVES) void xattn_partial_mfma_kernel(const fl
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float sv = Sx[c][r];
-        if (k0i + r >= S || (use_mask && rba_sigmoid(mv[r]) < 0.5f)) sv = -INFINITY;
+        if (k0i + r >= S || (use_mask && rba_mask_blocked(mv[r]))) sv = -INFINITY;
         Sx[c][r] = sv;
         cmax = fmaxf(cmax, sv);
       }

@@ -350,6 +350,72 @@ def test_k3_masked_xattn(ops, B, Q, S, nH, split):
     assert maxerr(ops.masked_xattn(dev(q), dev(k), dev(v), None, split_keys=split), ref0) < 5e-6
 
 
+def _f32_from_bits(bits):
+    return float(np.array([bits], dtype=np.uint32).view(np.float32)[0])
+
+
+_SIGMOID_BOUNDARY = []
+
+
+def _torch_sigmoid_boundary():
+    """Bisection over the bit patterns of the negative floats (more bits = further from zero) for the first x with torch's fp32 `sigmoid(x) < 0.5` -> (bits of the
+    last un-blocked float, bits of the first blocked one).  Evaluated on 9 copies so that the vectorised body and the scalar tail of the CPU kernel both answer."""
+    if not _SIGMOID_BOUNDARY:
+        def is_blocked(bits):
+            d = torch.full((9,), _f32_from_bits(bits), dtype=torch.float32).sigmoid() < 0.5
+            assert bool(d.all()) == bool(d.any())
+            return bool(d.all())
+        lo, hi = 0x80000000, 0xBF800000                       # -0.0 (not blocked) ... -1.0 (blocked)
+        assert not is_blocked(lo) and is_blocked(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (lo, mid) if is_blocked(mid) else (mid, hi)
+        _SIGMOID_BOUNDARY.append((lo, hi))
+    return _SIGMOID_BOUNDARY[0]
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("B,Q,S,nH", [(1, 16, 77, 2), (1, 37, 301, 3), (1, 100, 920, 8)])
+def test_k3_threshold_decision_at_the_boundary(ops, B, Q, S, nH, split):
+    """K3 fuses the reference's `sigmoid(mask) < 0.5` (mask2former_transformer_decoder.py:486).  The shape sweep aligns the oracle to the product's decisions as
+    torch would take them from the product's logits (tests/_sweep_align.py), so all three forms of K3 -- the scalar kernel, the row-flag kernel and the MFMA partial
+    kernel -- must decide exactly like torch's fp32 sigmoid for every input, also within 1e-6 of zero where `randn * 3` logits never land: planted +-0, the
+    smallest denormals, +-2^-25 ... +-2^-22, +-1e-6 and the two floats on either side of torch's boundary, each at three keys of every row, whose `v` rows are ten
+    times larger than the others (one wrong decision moves the output by >~ 1e-4); a row whose only un-blocked key sits at the last un-blocked float; a row whose
+    only candidate sits at the first blocked float (fully blocked: attends everywhere, :433); a row whose only un-blocked key lies in the last 144-key chunk."""
+    last_open, first_blocked = _torch_sigmoid_boundary()
+    assert (last_open, first_blocked) == (0xB43FFFFE, 0xB43FFFFF)           # a torch that moves them must be seen (rba_mask_blocked holds the same constant)
+    planted = [0.0, -0.0, 1e-45, -1e-45, 2.0 ** -25, -2.0 ** -25, 2.0 ** -24, -2.0 ** -24, 2.0 ** -23, -2.0 ** -23,
+               _f32_from_bits(last_open), _f32_from_bits(first_blocked), 2.0 ** -22, -2.0 ** -22, 1e-6, -1e-6]
+    g = torch.Generator().manual_seed(7 * Q + S)
+    q, k, v = (torch.randn(B, n, nH, 32, generator=g) for n in (Q, S, S))
+    keys = torch.randperm(S - 2, generator=g)[:3 * len(planted) - 1]
+    keys = torch.cat([keys, torch.tensor([S - 2])])            # the planted key set (one of them in the last chunk), shared by all rows: v belongs to the key
+    v *= 0.1                                                   # the others; the planted keys keep the scale the 5e-6 bound of test_k3_masked_xattn was set for
+    v[:, keys] *= 10.0
+    ml = torch.where(torch.rand(B, Q, S, generator=g) < 0.5, -5.0, 5.0)
+    values = torch.tensor(planted, dtype=torch.float32).repeat(3)
+    assert values.view(torch.int32)[3].item() == -(2 ** 31) + 1 and values[1].signbit()     # the denormal and -0.0 survived the trip
+    for b in range(B):
+        for r in range(Q):
+            ml[b, r, keys[torch.randperm(len(keys), generator=g)]] = values
+    ml[:, 0] = -5.0
+    ml[:, 0, keys[5]] = _f32_from_bits(last_open)              # the only un-blocked key of the row
+    ml[:, 1] = -5.0
+    ml[:, 1, keys[7]] = _f32_from_bits(first_blocked)          # blocked like all the others: the row attends everywhere
+    if S > 300:
+        ml[:, 2] = -5.0
+        ml[:, 2, S - 2] = -0.0                                  # the only un-blocked key lies in the last chunk
+    blocked = ref_ops.attn_mask_from_logits(ml.clone())
+    assert int(blocked[0, 0].sum()) == S - 1 and int(blocked[0, 1].sum()) == 0 and (S <= 300 or int(blocked[0, 2].sum()) == S - 1)
+    ref = ref_ops.attention_core(q.double(), k.double(), v.double(), blocked)
+    out = ops.masked_xattn(dev(q), dev(k), dev(v), dev(ml), split_keys=split)
+    assert torch.isfinite(out).all()
+    err = maxerr(out, ref)
+    print(f"[k3 boundary] Q {Q} S {S} nH {nH} split {split}: max err {err:.3e}")
+    assert err < 5e-6
+
+
 # ----------------------------------------------------------------------------------- K4
 @pytest.mark.parametrize("mode", ["fp32", "f16x3"])
 @pytest.mark.parametrize("B,Q,C,h,w", [(1, 100, 256, 32, 64), (2, 16, 64, 15, 23), (1, 100, 256, 7, 9), (1, 3, 8, 1, 1), (1, 100, 256, 128, 512),

@@ -8,7 +8,8 @@ sizes in between.  Here:
 * the round-4 advisor's case -- the GroupNorm-moment epilogues of K6 on `H*W = 128 * odd` rows, on the knobs build with every value of rba_k6_rs and both
   stream hints -- is pinned (it shipped broken once: the moment buffer was written past its end);
 * >= 40 image sizes x {tiny1, tiny3} x stream hint {1, 3} x {f16x3, bf16x6}: product vs the oracle at the end-to-end bounds (|d sem_seg|, |d rba| < 1e-4, no argmax
-  flip outside the reference's near-ties), both K1 paths;
+  flip outside the reference's near-ties), both K1 paths -- and, in every run, the product's attention-mask logits vs the oracle's after the oracle's
+  `sigmoid < 0.5` decisions have been aligned to the product's (tests/_sweep_align.py: capped, deterministic, each inverted decision provably inside rounding noise);
 * the same at REAL channel widths (Swin-B / Swin-L widths, shallow depths so the CPU oracle stays in seconds) over the sizes whose 1/4, 1/8, 1/16 maps are
   128 * odd pixels, 352 x 1216 included -- that is where the wide kernels' launch forms (K6 256 x 128 / K-split / GN-moment / fold, K7 C = 128 / 192 / 256, one-kernel
   MLP) switch -- plus knob-forced forms that must not change a bit;
@@ -90,28 +91,6 @@ def _err(a, b):
     return (a.detach().cpu().double() - b.double()).abs().max().item()
 
 
-def _explained_by_threshold(image, sd, a, taps, outs, h, w, tol, band=2e-5):
-    """The reference's decoder thresholds its interpolated mask logits at sigmoid < 0.5 (mask2former_transformer_decoder.py:483-487).  A logit within rounding noise
-    of 0 may fall on either side in two correct fp32 implementations, and the masked attention then differs by far more than 1e-4: the reference's own
-    discontinuity.  PROOF, not assumption: re-run the oracle with the decision of the near-zero entries (|logit| < band; the last head call's mask is never used)
-    inverted -- one, two or three of them at a time, nearest to zero first -- and accept only if one of those runs reproduces every failing product output within `tol`."""
-    import itertools
-    logits = taps["am_logits"][:-1]
-    cand = [(float(l.view(-1)[j].abs()), ci, int(j)) for ci, l in enumerate(logits) for j in (l.abs().view(-1) < band).nonzero().flatten()]
-    cand = [(ci, j) for _, ci, j in sorted(cand)]                              # nearest to zero first: the likeliest to have fallen on the other side
-    if not cand or len(cand) > 12:
-        return False, f"{len(cand)} thresholded logits inside {band:.0e} of zero"
-    subsets = [(c,) for c in cand] + list(itertools.combinations(cand[:6], 2)) + list(itertools.combinations(cand[:4], 3))
-    for sub in subsets[:30]:                                                   # bounded: every try is one CPU forward of the oracle
-        toggles = {}
-        for ci, j in sub:
-            toggles.setdefault(ci, []).append(j)
-        ref_t = ref_model.forward(image, sd, a, toggles={k: torch.tensor(v) for k, v in toggles.items()})
-        if all(_check(o, ref_t, h, w, "", tol=tol)[0] for o in outs):
-            return True, f"inverting the threshold decision of {sub} (|logit| {[float(logits[ci].view(-1)[j].abs()) for ci, j in sub]}) reproduces the product"
-    return False, f"no inversion of up to three of {cand} reproduces the product"
-
-
 def _check(out, ref, h, w, what, tol=1e-4):
     assert out["sem_seg"].shape == (19, h, w) and out["rba"].shape == (h, w) and out["argmax"].shape == (h, w), what
     e_sem, e_rba = _err(out["sem_seg"], ref["sem_seg"]), _err(out["rba"], ref["rba"])
@@ -122,56 +101,71 @@ def _check(out, ref, h, w, what, tol=1e-4):
     return ok, (e_sem, e_rba, bad, int(flips.sum()))
 
 
-def _sweep_one(name, h, w, configs, canvas=None):
+def _sweep_one(name, h, w, configs):
+    """One case (model, size) over `configs` = (stream hint, arithmetic mode): EVERY run goes through tests/_sweep_align.py -- the product's attention-mask logits are
+    tapped, the fp32 and the float64 oracle are aligned to the product's threshold decisions (deterministically: at most one oracle re-run per head call, cached per
+    toggle set over the runs of the case), and the run is held to
+      * the cap of _sweep_align.MAX_TOGGLES inverted decisions,
+      * logit parity |P - R32| <= k * own at every entry of every head call (k = 3 for bf16x6, 5 for f16x3; own = max |R32 - R64| of the aligned oracles),
+      * every inverted decision inside the old 2e-5 band (scaled with the output tolerance, as the search this replaces scaled it),
+      * the outputs: within 1e-4 of the aligned fp32 oracle, or (1) within tol = max(1e-4, 3 * own_out) of the float64 truth, or -- only for a run with inverted
+        decisions, as before -- within tol of the aligned fp32 oracle.
+    A run without inverted decisions is compared with the untouched fp32 oracle exactly as before."""
     from rba_amd import ops
+    from tests import _sweep_align as SA
     model, a, sd = _model(name)
     image = _image(h, w)
-    taps = {}
-    ref = ref_model.forward(image, sd, a, taps=taps)
+    run32, run64 = SA.oracle_runs(image, sd, a)
     dev_image = image.cuda()
-    failures = []
+    problems = []
     prev_hint = ops.concurrent_streams()
     try:
         for i, (hint, mode) in enumerate(configs):
             ops.set_concurrent_streams(hint)
             model.fused_upsample = (i + h + w) % 2 == 0                       # both K1 paths over the sweep (fused x4 up-sample / materialised planes)
             with ops.split_mode(mode):
-                out = model([{"image": dev_image}], return_argmax=True)[0]
+                with SA.tap_attn_logits(model.sem_seg_head.predictor) as P:
+                    out = model([{"image": dev_image}], return_argmax=True)[0]
                 rba2, arg2 = model.rba_scores([{"image": dev_image}], return_argmax=True)[0]
             what = f"{name} {h}x{w} hint {hint} {mode} fused {model.fused_upsample}"
-            ok, nums = _check(out, ref, h, w, what)
             assert torch.equal(rba2, out["rba"]) and torch.equal(arg2, out["argmax"]), what       # the score-only path of the evaluator = the dict path, bit for bit
+            assert len(P) == a["dec_layers"], (what, len(P))
+            want = [SA.blocked(p) for p in P]                                 # K3's own decisions (test_k3_threshold_decision_at_the_boundary)
+            try:
+                toggles, (R32, ref) = SA.align(run32, want)
+                _, (R64, ref64) = SA.align(run64, want)
+            except SA.AlignmentError as e:
+                problems.append(f"{what}: {e}")
+                continue
+            # (1) is the SIZE ill-conditioned for fp32 itself?  A 32 x 32 canvas leaves 1 x 1 / 2 x 2 maps: GroupNorm(32) over two values, LayerNorm over near-equal
+            # rows -- the reference's own fp32 forward is then 1e-4 ... 4e-4 from the float64 forward of the same weights (measured: tiny3 at 5 x 7, 13 x 11,
+            # 32 x 32).  The product must be as close to the float64 truth as the reference's fp32 is (factor 3), and never worse than 1e-4 where the reference is
+            # better than that.
+            own_out = max(_err(ref["sem_seg"], ref64["sem_seg"]), _err(ref["rba"], ref64["rba"]))
+            tol = max(1e-4, 3 * own_out)
+            bad, stats = SA.logit_parity(P, R32, R64, toggles, mode, band=SA.OLD_BAND * (tol / 1e-4))
+            ok, nums = _check(out, ref, h, w, what)
             if not ok:
-                failures.append((what, nums, {k: v.cpu() for k, v in out.items()}))
+                ref64f = {k: (v.float() if v.is_floating_point() else v) for k, v in ref64.items()}
+                ok = _check(out, ref64f, h, w, what, tol=tol)[0] or (bool(toggles) and _check(out, ref, h, w, what, tol=tol)[0])
+            if not ok:
+                bad.append(f"outputs (|d sem|, |d rba|, argmax flips outside near-ties, all flips) {nums} vs the aligned oracle, tol {tol:.1e} "
+                           f"(reference fp32 is {own_out:.1e} from its float64)")
+            _log_parity(name, h, w, hint, mode, SA.n_toggles(toggles), stats, SA.K_PARITY[mode])
+            problems += [f"{what} ({SA.n_toggles(toggles)} inverted decisions, ratio {stats['ratio']:.2f}): {b}" for b in bad]
     finally:
         ops.set_concurrent_streams(prev_hint)
         model.fused_upsample = True
-    if not failures:
-        return
-    # (1) is the SIZE ill-conditioned for fp32 itself?  A 32 x 32 canvas leaves 1 x 1 / 2 x 2 maps: GroupNorm(32) over two values, LayerNorm over near-equal rows --
-    # the reference's own fp32 forward is then 1e-4 ... 4e-4 from the float64 forward of the same weights (measured: tiny3 at 5 x 7, 13 x 11, 32 x 32).  The product
-    # must be as close to the float64 truth as the reference's fp32 is (factor 3), and never worse than 1e-4 where the reference is better than that.
-    ref64 = _truth64(image, sd, a)
-    own = max(_err(ref["sem_seg"], ref64["sem_seg"]), _err(ref["rba"], ref64["rba"]))
-    tol = max(1e-4, 3 * own)
-    ref64f = {k: (v.float() if v.is_floating_point() else v) for k, v in ref64.items()}
-    still = [(what, nums, out) for what, nums, out in failures if not _check(out, ref64f, h, w, "", tol=tol)[0]]
-    if not still:
-        return
-    # (2) the reference's threshold discontinuity, demonstrated by re-running the oracle with the near-zero decisions inverted
-    ok, why = _explained_by_threshold(image, sd, a, taps, [o for _, _, o in still], h, w, tol)
-    assert ok, f"{[(what, nums) for what, nums, _ in still]}: vs float64 truth tol {tol:.1e} (reference fp32 is {own:.1e} from it); {why}"
-    print(f"[sweep] {name} {h}x{w}: {[what for what, _, _ in still]} differ from the reference through its own threshold discontinuity: {why}")
+    assert not problems, "\n".join(problems)
 
 
-def _truth64(image, sd, a):
-    """the oracle in float64 on the same weights: how far the reference's own fp32 forward is from exact arithmetic at this size"""
-    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
-    torch.set_default_dtype(torch.float64)
-    try:
-        return ref_model.forward(image.double(), sd64, a)
-    finally:
-        torch.set_default_dtype(torch.float32)
+def _log_parity(name, h, w, hint, mode, toggles, stats, k):
+    """RBA_SWEEP_PARITY_LOG=<file>: one row per run (profiles/sweep_logit_parity.txt is the default sweep's)"""
+    path = _os.environ.get("RBA_SWEEP_PARITY_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"{name:7s} {h:5d} {w:5d} {hint:2d} {mode:7s} ratio {stats['ratio']:8.3f} k {k:g} toggles {toggles:2d} near_zero {stats['near_zero']:3d} "
+                    f"max|P-R| {stats['max_diff']:.3e} own {stats['own']:.3e} old_band 2e-05\n")
 
 
 ALL_CONFIGS = [(1, "f16x3"), (3, "f16x3"), (1, "bf16x6"), (3, "bf16x6")]
