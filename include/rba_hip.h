@@ -35,6 +35,8 @@
  *   rba_mask_point_loss_fwd_f32 <- point_sample of the matched masks + sigmoid_ce_loss + dice_loss (criterion.py:23-68, 230-239);
  *   rba_mask_point_loss_bwd_f32    autograd's backward of the three
  *   rba_match_cost_f32          <- the cost matrix of HungarianMatcher.memory_efficient_forward (matcher.py:105-149)
+ *   rba_outlier_tail_fwd_f32    <- SetCriterion.outlier_loss behind its score map: F.interpolate(align_corners=True), the masked terms and
+ *   rba_outlier_tail_bwd_f32       means (criterion.py:474-518); autograd's backward of them
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -235,6 +237,34 @@ int rba_match_cost_workspace_f32(int Q, int T, int P, int64_t* bytes);
 int rba_match_cost_f32(const float* pred_masks, const float* tgt_masks, const float* coords, const float* cls_prob, const int64_t* tgt_ids,
                        float* cost, int Q, int T, int P, int h, int w, int H, int W, int K1, float w_mask, float w_class, float w_dice,
                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/* K9.  The tail of SetCriterion.outlier_loss behind the score map (mask2former/modeling/criterion.py:474-518; docs/kernels/K9.md): score [B,h,w] is
+ * upsampled to the labels' [B,H,W] as F.interpolate(mode="bilinear", align_corners=True) does -- scale = (h - 1) / (H - 1) as an fp32 quotient (0
+ * when H == 1), src = scale Y, y0 = (int)src, y1 = y0 + (y0 < h - 1), ly = src - y0, hy = 1 - ly, columns alike, s = hy (hx v00 + lx v01) +
+ * ly (hx v10 + lx v11) -- and reduced against labels (label_bytes = 8: int64, 1: uint8; 0 = inlier, 1 = outlier, anything else ignored):
+ *   label 0: d = s - thr_in    label 1: d = thr_out - s    term = relu(d)^2 | d^2 | |d|   (func 0 | 2 | 3)
+ *   stats = (sum_in, n_in, sum_out, n_out);  loss = sum_in / n_in, and with n_out > 0: 0.5 (sum_in / n_in + sum_out / n_out)
+ *   func 1: binary cross-entropy with logits against (label == 1) over all B H W pixels (ignored labels are target 0, as in the reference):
+ *           stats = (sum, B H W, 0, 0), loss = 0.5 sum / (B H W)
+ * Kept from the reference: without an outlier pixel the inlier mean is not halved, and without an inlier pixel the loss is NaN (the mean of
+ * nothing).  Per-workgroup partial sums go to `workspace` with plain stores and one workgroup adds them in a fixed order and forms the loss on the
+ * device: no float atomics, no host read, loss [1] and stats [4] bitwise reproducible from launch to launch.  `workspace`: device memory owned by
+ * the caller, 4-byte aligned, at least rba_outlier_tail_workspace_f32's byte count; its contents on entry do not matter.
+ *
+ * rba_outlier_tail_bwd_f32: grad_score [B,h,w] = *grad_loss d loss / d score, from the forward's inputs and `stats`; *grad_loss [1] and stats are read
+ * on the device.  Gather form, one thread per score pixel over the label pixels whose taps name it, the taps recomputed exactly as the forward
+ * does; written with plain stores whatever it held before, bitwise reproducible; a score pixel no label pixel samples (H < h) gets 0.
+ * Subgradients as torch: relu'(0) = 0, sign(0) = 0.  A thread's walk is H W / (h w) label pixels times ~4, so an axis with h == 1 is walked
+ * whole by every thread of it.
+ * Every B, h, w, H, W >= 1 with B H W and B h w < 2^31 (H == 1, W == 1, h == 1 and down-sampling included); anything else, another label_bytes
+ * or func, or a NULL pointer returns hipErrorInvalidValue without a launch. */
+int rba_outlier_tail_workspace_f32(int B, int H, int W, int64_t* bytes);
+int rba_outlier_tail_fwd_f32(const float* score, const void* labels, int label_bytes /* 1 or 8 */, int B, int h, int w, int H, int W, int func,
+                             float thr_in, float thr_out, float* workspace, float* loss /* [1] */,
+                             float* stats /* [4]: sum_in, n_in, sum_out, n_out */, void* stream);
+int rba_outlier_tail_bwd_f32(const float* score, const void* labels, int label_bytes, int B, int h, int w, int H, int W, int func,
+                             float thr_in, float thr_out, const float* stats, const float* grad_loss /* device, [1] */,
+                             float* grad_score /* [B,h,w] */, void* stream);
 
 /* K5.  Swin (shifted-)window attention core over a token map, fusing zero-pad to a multiple of the window,
  * cyclic shift, window partition, q*scale @ k^T + relative-position bias (+ shift mask), softmax, @ v,

@@ -45,6 +45,9 @@ SIGNATURES = {
     "rba_mask_point_loss_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, ctypes.c_float, _vp],
     "rba_match_cost_workspace_f32": [_i, _i, _i, _vp],
     "rba_match_cost_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp],
+    "rba_outlier_tail_workspace_f32": [_i, _i, _i, _vp],
+    "rba_outlier_tail_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp],
+    "rba_outlier_tail_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],

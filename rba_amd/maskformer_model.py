@@ -119,9 +119,13 @@ class MaskFormer(nn.Module):
         """-> (outputs, image_sizes, padded (H,W)): _predict_outputs for the outlier-supervised fine-tune of the two prediction heads.  Backbone and
         pixel decoder run under no_grad exactly as in `predict`; the predictor runs in the caller's grad mode with its ``differentiable_heads`` honoured, so
         ``outputs["pred_logits"]`` / ``["pred_masks"]`` carry the bits `predict` gives and a graph over the ten head tensors
-        (``criterion.outlier_loss(outputs, targets)["outlier_loss"].backward()``).  Eager launches only: graph replay is never used here."""
+        (``criterion.outlier_loss(outputs, targets)["outlier_loss"].backward()``); with the predictor's ``deep_supervision`` set too, so does every
+        ``aux_outputs`` entry.  Eager launches only: graph replay is never used here."""
         predictor = self.sem_seg_head.predictor
         if not getattr(predictor, "differentiable_heads", False):
+            if getattr(predictor, "deep_supervision", False):
+                raise ops.RbaHipError("finetune_outputs: predictor.deep_supervision is set without predictor.differentiable_heads; deep supervision "
+                                      "is the differentiable heads' aux_outputs, so set differentiable_heads = True as well")
             raise ops.RbaHipError("finetune_outputs: set model.sem_seg_head.predictor.differentiable_heads = True first (without it the outputs "
                                   "carry no autograd graph)")
         with torch.no_grad():

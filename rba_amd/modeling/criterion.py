@@ -2,14 +2,16 @@
 
 ``outlier_loss`` (criterion.py:435-553): the score of criterion.py:449-465 -- softmax / sigmoid, ``einsum("bqc,bqhw->bchw")``, tanh-sum |
 logsumexp | sum -- is K1 at the mask resolution (``ops.rba_reduce``), and its gradient is K1's backward kernel (``ops.rba_reduce_backward``).
-Everything around it is small and stays torch with autograd: the class softmax ([Q, K+1] per image), the ``align_corners=True`` upsample of
-the one-channel score map and the masked means.
+The tail behind the score map (criterion.py:474-518) -- the ``align_corners=True`` upsample of the one-channel score map to the labels' size, the
+per-class terms, the masked means and the halving rule -- is K9 (``ops.outlier_tail`` / ``ops.outlier_tail_backward`` behind
+``OutlierTailFunction``): the counts and the "any outlier pixel" decision stay on the device, so the loss performs no host synchronisation.  Only
+the class softmax ([Q, K+1] per image) stays torch.
 
 ``loss_masks`` (criterion.py:194-243): the uncertainty oversampling, the label sampling and the two point-sampled losses with their scatter
 backward are K8 (``ops.point_sample``, ``ops.mask_point_loss``, ``ops.mask_point_loss_backward``); no ``grid_sample`` call.  ``loss_labels``
 (criterion.py:174-192) is plain torch.  ``SetCriterion`` is the reference's ``forward`` over these three losses behind a matcher
-(``rba_amd.modeling.matcher``); the four PEBAL / DenseHybrid losses, gradients into ``aux_outputs``, data mappers and the trainer are not
-part of this library.
+(``rba_amd.modeling.matcher``), ``aux_outputs`` included: they carry a gradient when the decoder's ``deep_supervision`` is set beside
+``differentiable_heads``.  The four PEBAL / DenseHybrid losses, data mappers and the trainer are not part of this library.
 """
 import torch
 import torch.nn.functional as F
@@ -52,6 +54,28 @@ class RbaScoreFunction(Function):
                 torch.stack([gp for _, gp in grads]) if need_prob else None, None)
 
 
+class OutlierTailFunction(Function):
+    """``OutlierTailFunction.apply(score [B,h,w], labels [B,H,W] int64 | uint8, func, thr_in, thr_out) -> loss`` (a scalar): ``ops.outlier_tail``
+    (the very bits of a direct call), differentiable once with respect to ``score`` only through ``ops.outlier_tail_backward``.  Saved: score,
+    labels and the four sums.  No host synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, score, labels, func, thr_in, thr_out):
+        score, labels = score.contiguous(), labels.contiguous()
+        loss, stats = ops.outlier_tail(score, labels, func, thr_in, thr_out)
+        ctx.settings = (func, thr_in, thr_out)
+        ctx.save_for_backward(score, labels, stats)
+        return loss.view(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        score, labels, stats = ctx.saved_tensors
+        return ops.outlier_tail_backward(score, labels, stats, grad_loss.contiguous(), *ctx.settings), None, None, None, None
+
+
 def _score_mode(target, score_norm):
     if target == "nls":
         if score_norm not in _NLS_SCORES:
@@ -73,23 +97,11 @@ def outlier_loss(outputs, targets, *, target="nls", score_norm="tanh", func="squ
     if func not in FUNCS:
         raise ValueError(f"outlier_loss: func {func!r} is not built (built: {list(FUNCS)})")
     labels = torch.stack([t["outlier_masks"] for t in targets])                      # [B,H,W]
-    ood, ind = labels == 1, labels == 0
+    if labels.dtype not in (torch.int64, torch.uint8):
+        labels = torch.where(labels == 0, 0, torch.where(labels == 1, 1, 255)).to(torch.uint8)      # on the device, nothing read back
     cls_prob = F.softmax(outputs["pred_logits"], dim=-1)[..., :-1]
     score = RbaScoreFunction.apply(outputs["pred_masks"], cls_prob, mode)            # [B,h,w]
-    score = F.interpolate(score[:, None], size=labels.shape[-2:], mode="bilinear", align_corners=True)[:, 0]
-    if func == "binary_cross_entropy":
-        return {"outlier_loss": 0.5 * F.binary_cross_entropy_with_logits(score, ood.to(score.dtype))}
-    d_in, d_out = score[ind] - inlier_upper_threshold, outlier_lower_threshold - score[ood]
-    if func == "squared_hinge":
-        term = lambda d: F.relu(d).pow(2).mean()
-    elif func == "mse":
-        term = lambda d: d.pow(2).mean()
-    else:
-        term = lambda d: d.abs().mean()
-    loss = term(d_in)
-    if d_out.numel() > 0:
-        loss = 0.5 * (loss + term(d_out))
-    return {"outlier_loss": loss}
+    return {"outlier_loss": OutlierTailFunction.apply(score, labels, func, inlier_upper_threshold, outlier_lower_threshold)}
 
 
 # mask2former/config.py:188-227, the values in force after the file's last assignment of each key

@@ -241,10 +241,18 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
     ``mask_embed`` tensors.  Its forward runs the kernels of the inference path -- ``pred_logits`` and ``pred_masks`` are bit-identical to it -- and
     the contraction's backward is K4's backward kernel (``MaskLogitsFunction``).  ``mask_features`` and the decoder-layer output entering that
     call receive no gradient: everything upstream of it runs under ``torch.no_grad`` and is not differentiable in this library; ``aux_outputs``
-    stay as in inference (detached; ``pred_logits`` only on the sparse path).  Otherwise -- whatever ``self.training`` or ``requires_grad`` of
-    the parameters say -- the inference path runs, which builds no autograd graph."""
+    stay as in inference (detached; ``pred_logits`` only on the sparse path) unless ``deep_supervision`` is set too.  Otherwise -- whatever
+    ``self.training`` or ``requires_grad`` of the parameters say -- the inference path runs, which builds no autograd graph.
+
+    ``deep_supervision`` (attribute, default False; read only with ``differentiable_heads`` set and grad mode on) is the recipe's
+    DEEP_SUPERVISION: ``aux_outputs`` then has ``num_layers`` entries in the reference's ``_set_aux_loss`` order -- the head call before layer 0,
+    then the calls after layers 0 ... L-2 -- each with ``pred_logits`` and a dense ``pred_masks`` [B,Q,H/4,W/4] that carry a graph over the same
+    ten head tensors and nothing else.  Decoding is untouched (under ``no_grad``, sparse intermediate heads, the attention masks and final
+    outputs of inference); the differentiable evaluations are added behind it on the decoder-layer outputs it held at each head call, and
+    their values are the bits the inference forward returns with ``sparse_intermediate_heads = False``."""
 
     differentiable_heads = False
+    deep_supervision = False
     # forward() accepts the pixel decoder's DeferredMaskFeatures in place of the mask-feature tensor (MaskFormerHead asks for one when this is set)
     takes_deferred_mask_features = True
 
@@ -349,6 +357,16 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             e = _HeadLinearFunction.apply(e, layer.weight, layer.bias, i < self.mask_embed.num_layers - 1)
         return outputs_class, e.contiguous()
 
+    def _aux_heads_differentiable(self, outputs, mask_features):
+        """The intermediate head calls of deep supervision on `outputs` = the decoder-layer outputs [B,Q,C] entering them: the query side once on
+        their concatenation along the batch axis (row-wise kernels: the bits of one call each, and one backward pass), then one contraction per
+        call against the one `mask_features` -> [{"pred_logits", "pred_masks"}], every tensor with a graph over the ten head tensors only."""
+        B = outputs[0].shape[0]
+        cls, embed = self._query_side_heads_differentiable(torch.cat(outputs, dim=0))
+        feat = mask_features.detach()
+        return [{"pred_logits": cls[l * B:(l + 1) * B], "pred_masks": MaskLogitsFunction.apply(embed[l * B:(l + 1) * B], feat)}
+                for l in range(len(outputs))]
+
     def _initial_query_side(self, B, device):
         """The prediction heads BEFORE the first layer (reference :427-430) see `query_feat.weight` -- learnt parameters, not the image: decoder_norm, class_embed
         and the three mask_embed Linears of that call are constants of the checkpoint.  Computed once per (weights version, batch size) with the same kernels
@@ -423,7 +441,8 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
 
     def forward(self, x, mask_features, mask=None):
         """x: list of [B,C,h_l,w_l]; mask_features [B,md,H/4,W/4] -> dict(pred_logits, pred_masks, aux_outputs)
-        (reference :398-470).  With ``differentiable_heads`` and grad mode on, everything but the last head call runs under no_grad."""
+        (reference :398-470).  With ``differentiable_heads`` and grad mode on, everything but the last head call runs under no_grad; with
+        ``deep_supervision`` too, the intermediate head calls are evaluated once more behind it, differentiably (see the class)."""
         assert len(x) == self.num_feature_levels
         del mask
         differentiable = self.differentiable_heads and torch.is_grad_enabled()
@@ -432,14 +451,14 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             # decided HERE: inside frozen() grad mode reads off.  The differentiable last call wants the map (MaskLogitsFunction), as before
             mask_features = mask_features.materialize()
         with frozen():
-            output, mask_features, side, predictions_class, predictions_mask = self._decode(x, mask_features)
+            output, mask_features, side, predictions_class, predictions_mask, head_inputs = self._decode(x, mask_features)
         cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side)
-        out = {
-            "pred_logits": cls,
-            "pred_masks": msk,
-            "aux_outputs": [({"pred_logits": a, "pred_masks": b} if b is not None else {"pred_logits": a})
-                            for a, b in zip(predictions_class, predictions_mask)],
-        }
+        if differentiable and self.deep_supervision:
+            aux = self._aux_heads_differentiable(head_inputs, mask_features) if head_inputs else []
+        else:
+            aux = [({"pred_logits": a, "pred_masks": b} if b is not None else {"pred_logits": a})
+                   for a, b in zip(predictions_class, predictions_mask)]
+        out = {"pred_logits": cls, "pred_masks": msk, "aux_outputs": aux}
         if self.ood_prediction:
             with frozen():
                 out["ood_pred"] = self.ood_pred(mask_features)                       # reference :467-468
@@ -447,7 +466,8 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
 
     def _decode(self, x, mask_features):
         """Everything of forward before its last head call -> (decoder-layer output [B,Q,C], contiguous mask_features, the cached query side of that
-        call (only a decoder without layers has one), class and mask predictions of the intermediate calls)."""
+        call (only a decoder without layers has one), class and mask predictions of the intermediate calls, the decoder-layer outputs that entered
+        those calls)."""
         src, pos, size_list = [], [], []
         B = x[0].shape[0]
         for i in range(self.num_feature_levels):
@@ -466,14 +486,15 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             mask_features = mask_features.materialize()               # today's path from here on, bit for bit
         if not isinstance(mask_features, DeferredMaskFeatures):
             mask_features = mask_features.contiguous()
-        predictions_class, predictions_mask = [], []
+        predictions_class, predictions_mask, head_inputs = [], [], []
         if self.num_layers == 0:
-            return output, mask_features, side0, predictions_class, predictions_mask
+            return output, mask_features, side0, predictions_class, predictions_mask, head_inputs
         gathered = {}
         cls, msk, attn_logits = self.forward_prediction_heads(output, mask_features, size_list[0], True, need_masks=False, gathered=gathered,
                                                               query_side=side0)
         predictions_class.append(cls)
         predictions_mask.append(msk)
+        head_inputs.append(output)
         for i in range(self.num_layers):
             li = i % self.num_feature_levels
             output = self.transformer_cross_attention_layers[i](output, src[li], attn_logits, pos[li], query_embed)   # memory + pos: inside the key projection
@@ -485,4 +506,5 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
                 output, mask_features, size_list[(i + 1) % self.num_feature_levels], need_attn_mask=True, need_masks=False, gathered=gathered)
             predictions_class.append(cls)
             predictions_mask.append(msk)
-        return output, mask_features, None, predictions_class, predictions_mask
+            head_inputs.append(output)
+        return output, mask_features, None, predictions_class, predictions_mask, head_inputs

@@ -533,6 +533,60 @@ def match_cost(pred_masks, tgt_masks, coords, cls_prob, tgt_ids, cost_mask=1.0, 
     return cost
 
 
+TAIL_FUNCS = {"squared_hinge": 0, "binary_cross_entropy": 1, "mse": 2, "l1": 3}
+
+
+def _outlier_tail_args(score, labels, func):
+    """The argument block of K9: score fp32 contiguous [B,h,w], labels int64 or uint8 contiguous [B,H,W], every size >= 1 and B H W, B h w < 2^31,
+    func one of TAIL_FUNCS -> (B, h, w, H, W, bytes per label, func number)."""
+    _chk(score, "score", dim=3)
+    _chk(labels, "labels", dtype=torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64, dim=3)
+    if func not in TAIL_FUNCS:
+        raise RbaHipError(f"unknown func {func!r}; choose from {sorted(TAIL_FUNCS)}")
+    (B, h, w), (H, W) = score.shape, labels.shape[1:]
+    if labels.shape[0] != B or min(B, h, w, H, W) < 1 or max(B * H * W, B * h * w) >= 1 << 31:
+        raise RbaHipError(f"outlier_tail: score [B,h,w] and labels [B,H,W] of one B, all sizes >= 1, B H W and B h w < 2^31; got "
+                          f"{tuple(score.shape)} and {tuple(labels.shape)}")
+    return B, h, w, H, W, labels.element_size(), TAIL_FUNCS[func]
+
+
+def _outlier_tail_workspace(device, nbytes):
+    """outlier_tail's per-workgroup partial sums: per (device, stream) and grow-only like K1 / K4 backward's; the kernel writes every word it later reads."""
+    return _stream_workspace("outlier_tail", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+
+
+@_hip_op
+def outlier_tail(score, labels, func, thr_in, thr_out):
+    """K9.  The reference's outlier loss behind its score map (criterion.py:474-518): score [B,h,w] upsampled to labels [B,H,W] (int64 or uint8;
+    0 = inlier, 1 = outlier, anything else ignored) as F.interpolate(align_corners=True) does, the terms of `func` (TAIL_FUNCS) against the two
+    thresholds, the masked means and the halving rule -> (loss [1], stats [4] = (sum_in, n_in, sum_out, n_out) for the backward;
+    "binary_cross_entropy": (sum, B H W, 0, 0)).  No outlier pixel: the inlier mean is not halved; no inlier pixel: NaN.  Nothing is read back
+    to the host; both results are bitwise reproducible from launch to launch."""
+    B, h, w, H, W, nb, f = _outlier_tail_args(score, labels, func)
+    dev = score.device
+    n = ctypes.c_int64(0)
+    _lib.check(_query("rba_outlier_tail_workspace_f32", B, H, W, ctypes.addressof(n)), "rba_outlier_tail_workspace_f32")
+    ws = _outlier_tail_workspace(dev, int(n.value))
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    stats = torch.empty((4,), dtype=torch.float32, device=dev)
+    _launch("rba_outlier_tail_fwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, f, float(thr_in), float(thr_out), _p(ws), _p(loss), _p(stats))
+    return loss, stats
+
+
+@_hip_op
+def outlier_tail_backward(score, labels, stats, grad_loss, func, thr_in, thr_out):
+    """K9.  outlier_tail's inputs and `stats`, and the upstream gradient as a one-element fp32 device tensor (read on the device) -> grad_score
+    [B,h,w], bitwise reproducible from launch to launch; a score pixel no label pixel samples gets 0."""
+    B, h, w, H, W, nb, f = _outlier_tail_args(score, labels, func)
+    _shaped(stats, "stats", (4,))
+    if _chk(grad_loss, "grad_loss").numel() != 1:
+        raise RbaHipError(f"grad_loss must have one element, got shape {tuple(grad_loss.shape)}")
+    grad = torch.empty((B, h, w), dtype=torch.float32, device=score.device)
+    _launch("rba_outlier_tail_bwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, f, float(thr_in), float(thr_out), _p(stats), _p(grad_loss),
+            _p(grad))
+    return grad
+
+
 @_hip_op
 def swin_bias_fragments(rel_bias, window_size):
     """[nH,N,N] gathered relative-position bias -> the MFMA-fragment-ordered copy K5 reads with coalesced loads."""
