@@ -22,6 +22,7 @@
  *   rba_reduce_f32              <- MaskFormer.semantic_inference (mask2former/maskformer_model.py:381-386)
  *                                  + get_RbA (evaluate_ood.py:143-150) + argmax (support.py:385-388)
  *   rba_reduce_bwd_f32          <- autograd's backward of SetCriterion.outlier_loss's score (mask2former/modeling/criterion.py:449-463)
+ *   rba_sem_seg_bwd_f32         <- autograd's backward of the class map einsum("bqc,bqhw->bchw", softmax, sigmoid) (criterion.py:394-405)
  *   rba_reduce_up4_f32          <- the same preceded by the x4 mask upsample (maskformer_model.py:294-299)
  *                                  and followed by the sem_seg_postprocess crop (maskformer_model.py:330-332)
  *   rba_resample_bilinear_f32   <- F.interpolate(mode="bilinear", align_corners=False) call sites
@@ -37,6 +38,8 @@
  *   rba_match_cost_f32          <- the cost matrix of HungarianMatcher.memory_efficient_forward (matcher.py:105-149)
  *   rba_outlier_tail_fwd_f32    <- SetCriterion.outlier_loss behind its score map: F.interpolate(align_corners=True), the masked terms and
  *   rba_outlier_tail_bwd_f32       means (criterion.py:474-518); autograd's backward of them
+ *   rba_dense_hybrid_loss_fwd_f32 <- SetCriterion.densehybrid_loss behind its class map: the two F.interpolate(align_corners=True), log_softmax,
+ *   rba_dense_hybrid_loss_bwd_f32    logsumexp, get_batch_avg and the two nll_loss (criterion.py:93-97, 406-431); autograd's backward of them
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -110,6 +113,15 @@ int rba_reduce_bwd_f32(const float* mask, const float* cls_prob, const float* gr
                        float* grad_mask /* [Q,HW] or NULL */, float* grad_prob /* [Q,K] or NULL */,
                        int Q, int K, int64_t HW, int score_mode,
                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The per-class adjoint of K1: the same kernel with u[k,p] = grad_sem[k,p] given instead of derived from a one-channel grad_score -- the
+ * gradients of sem_seg[k,p] = sum_q cls_prob[q,k] sigmoid(mask[q,p]) (rba_reduce_f32's sem_seg output; K10's input) with respect to mask and
+ * cls_prob, given grad_sem [K,HW] = dL/d sem_seg:  grad_mask[q,p] = sig (1 - sig) sum_k cls_prob[q,k] grad_sem[k,p],  grad_prob[q,k] =
+ * sum_p sig[q,p] grad_sem[k,p].  Tiling, workspace (rba_reduce_bwd_workspace_f32), fixed-order sum, optional outputs, domain and refusals are
+ * rba_reduce_bwd_f32's. */
+int rba_sem_seg_bwd_f32(const float* mask, const float* cls_prob, const float* grad_sem /* [K,HW] */,
+                        float* grad_mask /* [Q,HW] or NULL */, float* grad_prob /* [Q,K] or NULL */,
+                        int Q, int K, int64_t HW, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Bilinear resample, align_corners=False, no antialias (ATen upsample_bilinear2d semantics):
  * in [C,h,w] -> out [C,H,W];  if `add` != NULL (same shape as out): out = resample(in) + add. */
@@ -265,6 +277,36 @@ int rba_outlier_tail_fwd_f32(const float* score, const void* labels, int label_b
 int rba_outlier_tail_bwd_f32(const float* score, const void* labels, int label_bytes, int B, int h, int w, int H, int W, int func,
                              float thr_in, float thr_out, const float* stats, const float* grad_loss /* device, [1] */,
                              float* grad_score /* [B,h,w] */, void* stream);
+
+/* K10.  SetCriterion.densehybrid_loss behind its class map (mask2former/modeling/criterion.py:406-431; docs/kernels/K10.md).  sem [B,K,h,w] (the
+ * class map einsum("bqc,bqhw->bchw", softmax(cls)[..., :-1], sigmoid(mask))) and ood [B,2,h,w] (ood_pred) are sampled at every label pixel as
+ * F.interpolate(mode="bilinear", align_corners=True) does (K9's tap arithmetic) -- the up-sampled maps are never written -- and reduced against
+ * labels [B,H,W] (label_bytes = 8: int64, 1: uint8; < K: that class, 254: outlier, anything else ignored by the segmentation term).  Per pixel
+ * x_k, o_c = the samples, L = logsumexp_k x_k:
+ *   S_seg = sum_{label<K} (L - x_label), n_seg        S_ood = sum_{label=254} L, n_ood
+ *   S_th = sum over ALL B H W pixels of (logsumexp_c o_c - o_[label=254]) (void pixels are target 0, as in the reference)   S_x = sum_all sum_k x_k
+ *   m = S_x / (B K H W) (get_batch_avg; detached in the reference, no gradient here)
+ *   loss_seg = S_seg / n_seg   loss_ood = S_ood / n_ood - m   loss_th = S_th / (B H W)   loss = loss_seg + beta loss_ood + 10 beta loss_th
+ *   losses [4] = (loss, loss_seg, loss_ood, loss_th);  stats [8] = (S_seg, S_ood, S_th, S_x, n_seg, n_ood, B H W, m);  lse [B,H,W] = L
+ * n_seg == 0 or n_ood == 0 gives NaN, the mean of nothing, as in the reference.  Per-workgroup partial sums (counts as integers) go to
+ * `workspace` with plain stores and one workgroup adds them in a fixed order: no float atomics, no host read, every output bitwise reproducible
+ * from launch to launch.  `workspace`: device memory owned by the caller, 4-byte aligned, at least rba_dense_hybrid_loss_workspace_f32's byte
+ * count; its contents on entry do not matter.
+ *
+ * rba_dense_hybrid_loss_bwd_f32: with g = *grad_loss (the gradient of losses[0]; read on the device like stats), p_k = exp(x_k - L), q = softmax(o):
+ *   d / d x_k (P) = g ([label<K] (p_k - [k = label]) / n_seg + beta [label=254] p_k / n_ood)     d / d o_c (P) = g 10 beta (q_c - [c = [label=254]]) / (B H W)
+ * pulled back through the bilinear weights into grad_sem [B,K,h,w] and grad_ood [B,2,h,w].  Gather form: 16 lanes own one quarter-resolution pixel
+ * and share the label pixels whose taps name it, the taps recomputed exactly as the forward does, L read from `lse`; a fixed order, plain stores
+ * whatever the outputs held before, bitwise reproducible; a pixel no label pixel samples (H < h) gets 0.
+ * Every B, h, w, H, W >= 1 with B H W and B K h w < 2^31 (non-integer ratios, down-sampling, h == 1 included), 1 <= K <= 32; anything else, another
+ * label_bytes or a NULL pointer returns hipErrorInvalidValue without a launch. */
+int rba_dense_hybrid_loss_workspace_f32(int B, int H, int W, int64_t* bytes);
+int rba_dense_hybrid_loss_fwd_f32(const float* sem, const float* ood, const void* labels, int label_bytes /* 1 or 8 */, int B, int K, int h, int w,
+                                  int H, int W, float beta, float* workspace, float* losses /* [4] */, float* stats /* [8] */,
+                                  float* lse /* [B,H,W] */, void* stream);
+int rba_dense_hybrid_loss_bwd_f32(const float* sem, const float* ood, const void* labels, int label_bytes, const float* lse, int B, int K, int h,
+                                  int w, int H, int W, float beta, const float* stats, const float* grad_loss /* device, [1] */,
+                                  float* grad_sem /* [B,K,h,w] */, float* grad_ood /* [B,2,h,w] */, void* stream);
 
 /* K5.  Swin (shifted-)window attention core over a token map, fusing zero-pad to a multiple of the window,
  * cyclic shift, window partition, q*scale @ k^T + relative-position bias (+ shift mask), softmax, @ v,

@@ -25,6 +25,7 @@ SIGNATURES = {
     "rba_reduce_up4_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_reduce_bwd_workspace_f32": [_i, _i, _i64, _vp],
     "rba_reduce_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i64, _vp],
+    "rba_sem_seg_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i64, _vp],
     "rba_resample_bilinear_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_ms_deform_attn_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_ms_deform_attn_fwd_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -48,6 +49,9 @@ SIGNATURES = {
     "rba_outlier_tail_workspace_f32": [_i, _i, _i, _vp],
     "rba_outlier_tail_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp],
     "rba_outlier_tail_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp],
+    "rba_dense_hybrid_loss_workspace_f32": [_i, _i, _i, _vp],
+    "rba_dense_hybrid_loss_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
+    "rba_dense_hybrid_loss_bwd_f32": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],

@@ -8,9 +8,9 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip",
+SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip",
            "swin_window_attn.hip", "swin_attn_block.hip", "group_norm.hip", "layer_norm.hip", "skinny_linear.hip", "split_linear.hip", "split_linear_dma.hip", "split_linear_gnf.hip", "gaussian_blur.hip", "open_panoptic.hip", "dense_hybrid.hip", "patch_embed.hip", "token_linear.hip", "decoder_small.hip"]
-HEADERS = ["common.h", "knobs.h", "rba_reduce_kernels.h", "split_linear_dma.h", "split_linear_h3.h", "split_linear_h3q.h", "mlp_fused_h3.h", "swin_window_attn_h3.h", "swin_attn_block.h",
+HEADERS = ["common.h", "knobs.h", "bilinear_ac.h", "rba_reduce_kernels.h", "split_linear_dma.h", "split_linear_h3.h", "split_linear_h3q.h", "mlp_fused_h3.h", "swin_window_attn_h3.h", "swin_attn_block.h",
            os.path.join("..", "..", "include", "rba_hip.h")]
 TUNE_SOURCES = [os.path.join("tune", "rba_reduce_tune.hip"), os.path.join("tune", "split_linear_tune.hip"), os.path.join("tune", "split_linear_ws.hip"), os.path.join("tune", "mlp_fused_h1.hip"), os.path.join("tune", "k5_timing.hip"), os.path.join("tune", "k5_wpe_ab.hip"), os.path.join("tune", "k5_wpe_plain.hip"), os.path.join("tune", "k5_persist.hip"), os.path.join("tune", "k7_timing.hip")] + [os.path.join("tune", f"gnf_form{f}_dbg{d}.hip") for f in (0, 1) for d in (0, 1)] + [os.path.join("tune", "gnf_form0_dbg1_unpacked.hip"), os.path.join("tune", "gnf_form1_dbg0_unpacked.hip")]
 TUNE_LIB = os.path.join(HERE, "tune", "librba_tune.so")
@@ -35,7 +35,8 @@ MFMA_SOURCES = ({"split_linear.hip", "split_linear_dma.hip", "mask_logits.hip", 
 # ms_deform_attn_bwd.hip: atomic-bound (docs/kernels/K2.md), and the compiler packed its tap differences into the cross-select form the gate refuses (rule P).
 # point_loss.hip: gather-bound, and the compiler packed the matcher's accumulator pairs into the same cross-select form (v_pk_add_f32 ... op_sel:[0,1]).
 # outlier_tail.hip: bound by its label reads, and the compiler packed the two class sums' wave reduction into the same form (v_pk_add_f32 ... op_sel:[0,1]).
-UNPACKED_ALWAYS = {"split_linear_gnf.hip", "ms_deform_attn_bwd.hip", "point_loss.hip", "outlier_tail.hip"}
+# dense_hybrid_loss.hip: bound by its gathers, and the compiler packed the backward's two ood samples into the same form (v_pk_mul_f32 / v_pk_fma_f32 ... op_sel:[0,1]).
+UNPACKED_ALWAYS = {"split_linear_gnf.hip", "ms_deform_attn_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip"}
 UNPACKED_SOURCES = MFMA_SOURCES | UNPACKED_ALWAYS
 
 

@@ -2,7 +2,7 @@
 // bilinear upsample of the one-channel score [B,h,w] to the labels' [B,H,W], the per-pixel term, the masked means, the halving rule -- and all of
 // it backward.  fp32, wave64, no MFMA, no LDS beyond the reduction's 16 words per wave, no scratch.  docs/kernels/K9.md.
 //
-// Upsample (tap_of): torch's upsample_bilinear2d with align_corners=True -- scale = (in - 1) / (out - 1) as an fp32 quotient (0 when out == 1),
+// Upsample (tap_of, bilinear_ac.h -- shared with K10): torch's upsample_bilinear2d with align_corners=True -- scale = (in - 1) / (out - 1) as an fp32 quotient (0 when out == 1),
 // src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), l = src - i0, h = 1 - l; value = hy (hx v00 + lx v01) + ly (hx v10 + lx v11).
 // Forward and backward call the same function, so the backward's taps and weights are the forward's bits.
 //
@@ -19,38 +19,12 @@
 //     not name the pixel, recomputes the upsampled score there and adds weight * d term / d s * the class factor from `stats` and *grad_loss
 //     (both read on the device).  Plain stores, a fixed loop order: bitwise reproducible; a pixel nobody samples (H < h) gets 0.
 //     Subgradients as torch: relu'(0) = 0, sign(0) = 0.
-#include <math.h>
-#include "common.h"
+#include "bilinear_ac.h"
 #include "../../include/rba_hip.h"
 
 namespace {
 
 constexpr int OT_THREADS = 256, OT_MAX_GROUPS = 2048, OT_PER_THREAD = 4;
-
-struct AcTap {
-  int i0, i1;
-  float l, h;
-};
-
-__host__ __device__ __forceinline__ float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
-
-__device__ __forceinline__ AcTap tap_of(int dst, float scale, int in) {
-  const float src = scale * (float)dst;
-  int i0 = (int)src;                                    // src >= 0: trunc == floor
-  i0 = i0 < in - 1 ? i0 : in - 1;                       // never past the map, whatever the product's rounding
-  AcTap t;
-  t.i0 = i0;
-  t.i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  t.l = src - (float)i0;
-  t.h = 1.0f - t.l;
-  return t;
-}
-
-__device__ __forceinline__ float upsampled(const float* __restrict__ plane, int w, const AcTap& ty, const AcTap& tx) {
-  const float* r0 = plane + (int64_t)ty.i0 * w;
-  const float* r1 = plane + (int64_t)ty.i1 * w;
-  return ty.h * (tx.h * r0[tx.i0] + tx.l * r0[tx.i1]) + ty.l * (tx.h * r1[tx.i0] + tx.l * r1[tx.i1]);
-}
 
 // 0 = inlier, 1 = outlier, anything else = ignored
 __device__ __forceinline__ int label_at(const void* __restrict__ labels, int label_bytes, int64_t i) {
@@ -83,12 +57,6 @@ __device__ __forceinline__ float dterm_of(float d) {
   } else {
     return d > 0.f ? 1.0f : d < 0.f ? -1.0f : 0.f;
   }
-}
-
-__device__ __forceinline__ int wave_reduce_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, RBA_WAVE);
-  return v;
 }
 
 int groups_of(int64_t total) {
@@ -187,20 +155,6 @@ __global__ __launch_bounds__(OT_THREADS) void tail_finish_kernel(const float* __
       if (nc > 0) L = 0.5f * (L + c / (float)nc);
       *loss = L;
     }
-  }
-}
-
-// the label rows / columns [lo, hi] whose source coordinate scale * dst can lie in (p - 1, p + 1), one wider on each side, clamped to [0, out - 1]
-__device__ __forceinline__ void candidates(int p, float scale, int out, int& lo, int& hi) {
-  lo = 0;
-  hi = out - 1;
-  if (scale > 0.f) {
-    // (the 1e-6 covers the rounding of scale * dst and of the two quotients, four relative errors of 2^-24 at the most)
-    const float a = fmaxf(floorf((float)(p - 1) / scale * (1.0f - 1e-6f)) - 1.0f, 0.f);
-    const float b = fmaxf(ceilf((float)(p + 1) / scale * (1.0f + 1e-6f)) + 1.0f, 0.f);
-    const int64_t top = out - 1, ia = (int64_t)fminf(a, 4e9f), ib = (int64_t)fminf(b, 4e9f);
-    lo = (int)(ia < top ? ia : top);
-    hi = (int)(ib < top ? ib : top);
   }
 }
 

@@ -18,6 +18,9 @@
 // LDS rows are TILE + 4 floats.  While (Q + K) rows fit 64 KiB (Q = 100, K = 19: 61 KiB, two workgroups per CU) the whole sig tile stays
 // resident; beyond that the kernel walks the queries in chunks of QC rows and phase 3 reloads the mask tile (L2 / MALL resident by then)
 // and recomputes sig -- the same arithmetic, so both forms give the same bits.
+//
+// PER_CLASS = the adjoint of the class map itself (rba_sem_seg_bwd_f32; sem[k,n] = s[k,n] is K10's input): u[k,n] = grad_sem[k,n] is LOADED in
+// phase 2 instead of derived from a one-channel gradient, so phase 1 keeps only the sigmoids.  Same tiling, workspace and fixed-order sum.
 #include "common.h"
 #include "../../include/rba_hip.h"
 
@@ -28,9 +31,9 @@ constexpr int TILE = 128, LDW = TILE + 4, ROWS_64K = 65536 / (LDW * 4);   // 124
 // 1 / (1 + e^-x) with the accurate expf and a true division: x -> -inf gives 1 / inf = 0, x -> +inf gives 1 / 1 = 1, never NaN for finite x
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-template <int KMAX>
+template <int KMAX, bool PER_CLASS>
 __global__ __launch_bounds__(TILE) void rba_reduce_bwd_kernel(const float* __restrict__ mask, const float* __restrict__ prob,
-                                                              const float* __restrict__ gscore, float* __restrict__ gmask,
+                                                              const float* __restrict__ gscore /* PER_CLASS: grad_sem [K,HW] */, float* __restrict__ gmask,
                                                               float* __restrict__ part, int Q, int K, int64_t HW, int mode, int QC) {
   extern __shared__ __attribute__((aligned(16))) float k1b_lds[];
   float* sh_u = k1b_lds;                 // [K][LDW]
@@ -46,19 +49,30 @@ __global__ __launch_bounds__(TILE) void rba_reduce_bwd_kernel(const float* __res
   float acc[KMAX];
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) acc[k] = 0.f;
+  if constexpr (PER_CLASS) {
+    if (resident) {
 #pragma unroll 4
-  for (int q = 0; q < Q; ++q) {
-    const float s = sigmoid_acc(mp[(int64_t)q * HW]);
-    if (resident) sh_s[q * LDW + tid] = s;
-    const float* pq = prob + q * K;      // wave-uniform
+      for (int q = 0; q < Q; ++q) sh_s[q * LDW + tid] = sigmoid_acc(mp[(int64_t)q * HW]);
+    }
+  } else {
+#pragma unroll 4
+    for (int q = 0; q < Q; ++q) {
+      const float s = sigmoid_acc(mp[(int64_t)q * HW]);
+      if (resident) sh_s[q * LDW + tid] = s;
+      const float* pq = prob + q * K;      // wave-uniform
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) acc[k] = fmaf(pq[k], s, acc[k]);
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) acc[k] = fmaf(pq[k], s, acc[k]);
+    }
   }
 
   // ---- phase 2: acc[k] = u[k]
-  const float g = live ? gscore[n] : 0.f;
-  if (mode == 0) {
+  const float g = PER_CLASS || !live ? 0.f : gscore[n];
+  if constexpr (PER_CLASS) {
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) acc[k] = live ? gscore[(int64_t)k * HW + n] : 0.f;
+  } else if (mode == 0) {
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < K) {       // 1 - tanh^2 s = 4 E / (1 + E)^2 with E = e^(-2|s|): no cancellation where tanh s is within an ulp of 1
@@ -174,7 +188,7 @@ __global__ __launch_bounds__(256) void rba_reduce_bwd_sum_kernel(const float* __
 
 int64_t tiles_of(int64_t HW) { return (HW + TILE - 1) / TILE; }
 
-template <int KMAX>
+template <int KMAX, bool PER_CLASS>
 int launch_bwd(const float* mask, const float* prob, const float* gscore, float* gmask, float* part, int Q, int K, int64_t HW, int mode,
                hipStream_t st) {
   const int QC = Q + K <= ROWS_64K ? Q : min(Q, max(16, ROWS_64K - K));
@@ -185,9 +199,9 @@ int launch_bwd(const float* mask, const float* prob, const float* gscore, float*
   if (shm > SHM_MAX) return (int)hipErrorInvalidValue;
   if (shm > 65536) {
     static size_t lds_enabled[64];
-    if (const int rc = rba_dynamic_lds(rba_reduce_bwd_kernel<KMAX>, SHM_MAX, lds_enabled)) return rc;
+    if (const int rc = rba_dynamic_lds(rba_reduce_bwd_kernel<KMAX, PER_CLASS>, SHM_MAX, lds_enabled)) return rc;
   }
-  hipLaunchKernelGGL((rba_reduce_bwd_kernel<KMAX>), dim3((unsigned)tiles_of(HW)), dim3(TILE), shm, st, mask, prob, gscore, gmask, part, Q, K, HW,
+  hipLaunchKernelGGL((rba_reduce_bwd_kernel<KMAX, PER_CLASS>), dim3((unsigned)tiles_of(HW)), dim3(TILE), shm, st, mask, prob, gscore, gmask, part, Q, K, HW,
                      mode, QC);
   return rba_launch_status();
 }
@@ -196,6 +210,31 @@ bool domain_ok(int Q, int K, int64_t HW) {
   // 32-bit q * K and slice offsets inside the kernels, one workgroup per tile
   return Q >= 1 && K >= 1 && K <= 160 && HW >= 1 && (int64_t)Q * K <= 0x7fffffffLL && tiles_of(HW) <= 0x7fffffffLL &&
          tiles_of(HW) <= INT64_MAX / 4 / ((int64_t)Q * K);
+}
+
+// the body of both entry points: `grad` is grad_score [HW] (PER_CLASS false) or grad_sem [K,HW] (true, where `score_mode` is not read)
+template <bool PER_CLASS>
+int reduce_bwd(const float* mask, const float* cls_prob, const float* grad, float* grad_mask, float* grad_prob, int Q, int K, int64_t HW, int score_mode,
+               void* workspace, int64_t workspace_bytes, void* stream) {
+  RBA_CHECK_ARG(domain_ok(Q, K, HW) && score_mode >= 0 && score_mode <= 2);
+  RBA_CHECK_ARG(mask && cls_prob && grad && (grad_mask || grad_prob));
+  const int64_t tiles = tiles_of(HW);
+  float* part = nullptr;
+  if (grad_prob) {
+    RBA_CHECK_ARG(workspace && (((uintptr_t)workspace) & 3) == 0 && workspace_bytes >= tiles * Q * K * (int64_t)sizeof(float));
+    part = reinterpret_cast<float*>(workspace);
+  }
+  rba_begin();
+  hipStream_t st = (hipStream_t)stream;
+  int e;
+  if (K <= 20) e = launch_bwd<20, PER_CLASS>(mask, cls_prob, grad, grad_mask, part, Q, K, HW, score_mode, st);
+  else if (K <= 32) e = launch_bwd<32, PER_CLASS>(mask, cls_prob, grad, grad_mask, part, Q, K, HW, score_mode, st);
+  else if (K <= 80) e = launch_bwd<80, PER_CLASS>(mask, cls_prob, grad, grad_mask, part, Q, K, HW, score_mode, st);
+  else e = launch_bwd<160, PER_CLASS>(mask, cls_prob, grad, grad_mask, part, Q, K, HW, score_mode, st);
+  if (e != 0 || !grad_prob) return e;
+  const int QK = Q * K;
+  hipLaunchKernelGGL(rba_reduce_bwd_sum_kernel, dim3((unsigned)((QK + 63) / 64)), dim3(256), 0, st, part, grad_prob, QK, tiles);
+  return rba_launch_status();
 }
 
 }  // namespace
@@ -208,23 +247,10 @@ extern "C" int rba_reduce_bwd_workspace_f32(int Q, int K, int64_t HW, int64_t* b
 
 extern "C" int rba_reduce_bwd_f32(const float* mask, const float* cls_prob, const float* grad_score, float* grad_mask, float* grad_prob,
                                   int Q, int K, int64_t HW, int score_mode, void* workspace, int64_t workspace_bytes, void* stream) {
-  RBA_CHECK_ARG(domain_ok(Q, K, HW) && score_mode >= 0 && score_mode <= 2);
-  RBA_CHECK_ARG(mask && cls_prob && grad_score && (grad_mask || grad_prob));
-  const int64_t tiles = tiles_of(HW);
-  float* part = nullptr;
-  if (grad_prob) {
-    RBA_CHECK_ARG(workspace && (((uintptr_t)workspace) & 3) == 0 && workspace_bytes >= tiles * Q * K * (int64_t)sizeof(float));
-    part = reinterpret_cast<float*>(workspace);
-  }
-  rba_begin();
-  hipStream_t st = (hipStream_t)stream;
-  int e;
-  if (K <= 20) e = launch_bwd<20>(mask, cls_prob, grad_score, grad_mask, part, Q, K, HW, score_mode, st);
-  else if (K <= 32) e = launch_bwd<32>(mask, cls_prob, grad_score, grad_mask, part, Q, K, HW, score_mode, st);
-  else if (K <= 80) e = launch_bwd<80>(mask, cls_prob, grad_score, grad_mask, part, Q, K, HW, score_mode, st);
-  else e = launch_bwd<160>(mask, cls_prob, grad_score, grad_mask, part, Q, K, HW, score_mode, st);
-  if (e != 0 || !grad_prob) return e;
-  const int QK = Q * K;
-  hipLaunchKernelGGL(rba_reduce_bwd_sum_kernel, dim3((unsigned)((QK + 63) / 64)), dim3(256), 0, st, part, grad_prob, QK, tiles);
-  return rba_launch_status();
+  return reduce_bwd<false>(mask, cls_prob, grad_score, grad_mask, grad_prob, Q, K, HW, score_mode, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rba_sem_seg_bwd_f32(const float* mask, const float* cls_prob, const float* grad_sem, float* grad_mask, float* grad_prob,
+                                   int Q, int K, int64_t HW, void* workspace, int64_t workspace_bytes, void* stream) {
+  return reduce_bwd<true>(mask, cls_prob, grad_sem, grad_mask, grad_prob, Q, K, HW, 0, workspace, workspace_bytes, stream);
 }

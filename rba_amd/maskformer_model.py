@@ -120,7 +120,10 @@ class MaskFormer(nn.Module):
         pixel decoder run under no_grad exactly as in `predict`; the predictor runs in the caller's grad mode with its ``differentiable_heads`` honoured, so
         ``outputs["pred_logits"]`` / ``["pred_masks"]`` carry the bits `predict` gives and a graph over the ten head tensors
         (``criterion.outlier_loss(outputs, targets)["outlier_loss"].backward()``); with the predictor's ``deep_supervision`` set too, so does every
-        ``aux_outputs`` entry.  Eager launches only: graph replay is never used here."""
+        ``aux_outputs`` entry.  On a model with the DenseHybrid head, ``outputs["ood_pred"]`` [B,2,H/4,W/4] is the inference kernel's output without
+        a graph, or -- with the predictor's ``differentiable_ood_head`` set -- the head in plain torch with a graph over its four parameters
+        (``criterion.densehybrid_loss(outputs, targets, num_classes=K)["densehybrid_loss"].backward()``).  Eager launches only: graph replay is never
+        used here."""
         predictor = self.sem_seg_head.predictor
         if not getattr(predictor, "differentiable_heads", False):
             if getattr(predictor, "deep_supervision", False):

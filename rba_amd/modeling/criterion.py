@@ -11,7 +11,15 @@ the class softmax ([Q, K+1] per image) stays torch.
 backward are K8 (``ops.point_sample``, ``ops.mask_point_loss``, ``ops.mask_point_loss_backward``); no ``grid_sample`` call.  ``loss_labels``
 (criterion.py:174-192) is plain torch.  ``SetCriterion`` is the reference's ``forward`` over these three losses behind a matcher
 (``rba_amd.modeling.matcher``), ``aux_outputs`` included: they carry a gradient when the decoder's ``deep_supervision`` is set beside
-``differentiable_heads``.  The four PEBAL / DenseHybrid losses, data mappers and the trainer are not part of this library.
+``differentiable_heads``.
+
+``densehybrid_loss`` (criterion.py:390-433), the whole criterion of the DenseHybrid fine-tune recipe (its loss list is ``["densehybrid"]`` alone,
+maskformer_model.py:166-169): the class map ``einsum("bqc,bqhw->bchw")`` is K1's ``sem_seg`` output at the mask resolution behind
+``SemSegFunction`` (backward: K1's per-class adjoint, ``ops.sem_seg_backward``), and everything behind it -- the two ``align_corners=True``
+upsamples to the labels' size, log_softmax, logsumexp, get_batch_avg and the two nll_loss -- is K10 (``ops.dense_hybrid_loss`` /
+``ops.dense_hybrid_loss_backward`` behind ``DenseHybridLossFunction``); the up-sampled maps never exist.  ``SetCriterion`` does not take
+"densehybrid": the function is called directly.  The gambler, smoothness and sparsity losses, data mappers and the trainer are not part of
+this library.
 """
 import torch
 import torch.nn.functional as F
@@ -123,6 +131,86 @@ def outlier_loss_from_cfg(cfg):
     if kw["func"] not in FUNCS:
         raise ValueError(f"outlier_loss: func {kw['func']!r} is not built (built: {list(FUNCS)})")
     return functools.partial(outlier_loss, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the DenseHybrid loss (K10)
+class SemSegFunction(Function):
+    """``SemSegFunction.apply(mask_pred [B,Q,h,w], cls_prob [B,Q,K]) -> [B,K,h,w]``: the class map of ``ops.rba_reduce(..., want_sem_seg=True)``
+    image by image (the very bits of a direct call), differentiable once with respect to both tensors through ``ops.sem_seg_backward``.  Only
+    the two inputs are saved; a gradient nobody asks for is not computed."""
+
+    @staticmethod
+    def forward(ctx, mask_pred, cls_prob):
+        if mask_pred.dim() != 4 or cls_prob.dim() != 3 or cls_prob.shape[:2] != mask_pred.shape[:2]:
+            raise ops.RbaHipError(f"SemSegFunction: mask_pred [B,Q,h,w] and cls_prob [B,Q,K], got {tuple(mask_pred.shape)} and {tuple(cls_prob.shape)}")
+        mask_pred, cls_prob = mask_pred.contiguous(), cls_prob.contiguous()
+        ctx.save_for_backward(mask_pred, cls_prob)
+        return torch.stack([ops.rba_reduce(m, p, want_sem_seg=True)[1] for m, p in zip(mask_pred, cls_prob)])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_sem):
+        mask_pred, cls_prob = ctx.saved_tensors
+        need_mask, need_prob = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_mask or need_prob):
+            return None, None
+        grad_sem = grad_sem.contiguous()
+        grads = [ops.sem_seg_backward(m, p, g, need_mask=need_mask, need_prob=need_prob) for m, p, g in zip(mask_pred, cls_prob, grad_sem)]
+        return (torch.stack([gm for gm, _ in grads]) if need_mask else None,
+                torch.stack([gp for _, gp in grads]) if need_prob else None)
+
+
+class DenseHybridLossFunction(Function):
+    """``DenseHybridLossFunction.apply(sem [B,K,h,w], ood [B,2,h,w], labels [B,H,W] int64 | uint8, beta) -> loss`` (a scalar):
+    ``ops.dense_hybrid_loss`` (losses[0], the very bits of a direct call), differentiable once with respect to ``sem`` and ``ood`` through
+    ``ops.dense_hybrid_loss_backward``.  Saved: the three inputs, the sums and the [B,H,W] logsumexp map.  No host synchronisation in either
+    direction."""
+
+    @staticmethod
+    def forward(ctx, sem, ood, labels, beta):
+        sem, ood, labels = sem.contiguous(), ood.contiguous(), labels.contiguous()
+        losses, stats, lse = ops.dense_hybrid_loss(sem, ood, labels, beta)
+        ctx.beta = beta
+        ctx.save_for_backward(sem, ood, labels, stats, lse)
+        return losses[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        need_sem, need_ood = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_sem or need_ood):
+            return None, None, None, None
+        sem, ood, labels, stats, lse = ctx.saved_tensors
+        grad_sem, grad_ood = ops.dense_hybrid_loss_backward(sem, ood, labels, stats, lse, grad_loss.contiguous(), ctx.beta)
+        return grad_sem if need_sem else None, grad_ood if need_ood else None, None, None
+
+
+def densehybrid_loss(outputs, targets, *, num_classes, beta=0.03):
+    """``SetCriterion.densehybrid_loss`` (criterion.py:390-433; the matcher's ``indices`` and ``num_masks`` are unused there and absent here).
+    outputs["pred_logits"] [B,Q,K+1], outputs["pred_masks"] [B,Q,h,w], outputs["ood_pred"] [B,2,h,w]; targets[i]["sem_seg"] [H,W] with a value
+    < K = that class, 254 = outlier, anything else void (the reference takes 255 only and relabels its targets in place; here they are not
+    written) -> {"densehybrid_loss": scalar}.  ``num_classes`` = K is checked against ``pred_logits``.  Kept from the reference: without a class
+    pixel or without an outlier pixel the loss is NaN (the mean of nothing)."""
+    K = outputs["pred_logits"].shape[-1] - 1
+    if K != num_classes:
+        raise ValueError(f"densehybrid_loss: pred_logits has {K} classes (and no-object), num_classes is {num_classes}")
+    labels = torch.stack([t["sem_seg"] for t in targets])                            # [B,H,W]
+    if labels.dtype not in (torch.int64, torch.uint8):
+        keep = ((labels >= 0) & (labels < K)) | (labels == 254)
+        labels = torch.where(keep, labels, 255).to(torch.uint8)                      # on the device, nothing read back
+    cls_prob = F.softmax(outputs["pred_logits"], dim=-1)[..., :-1]
+    sem = SemSegFunction.apply(outputs["pred_masks"], cls_prob)                      # [B,K,h,w]
+    return {"densehybrid_loss": DenseHybridLossFunction.apply(sem, outputs["ood_pred"], labels, float(beta))}
+
+
+def densehybrid_loss_from_cfg(cfg):
+    """The loss the DenseHybrid recipe's config selects: reads MODEL.MASK_FORMER.DENSE_HYBRID_BETA (absent: 0.03, mask2former/config.py) and
+    MODEL.SEM_SEG_HEAD.NUM_CLASSES of ``rba_amd.config.load_cfg``'s result and returns ``loss(outputs, targets)``, a closure over
+    ``densehybrid_loss``; its ``.keywords`` holds the two settings."""
+    import functools
+    model = cfg.get("MODEL", {})
+    return functools.partial(densehybrid_loss, num_classes=int(model.get("SEM_SEG_HEAD", {}).get("NUM_CLASSES", 19)),
+                             beta=float(model.get("MASK_FORMER", {}).get("DENSE_HYBRID_BETA", 0.03)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the point-sampled mask losses (K8)

@@ -232,6 +232,17 @@ class BNReluConv(nn.Module):
         return ops.bn_relu_conv1x1(x.contiguous(), scale.contiguous(), shift.contiguous(),
                                    self.conv.weight.flatten(1).contiguous(), self.conv.bias)
 
+    def forward_differentiable(self, x):
+        """The head in plain torch, with a graph over its four parameters (the DenseHybrid fine-tune trains it; see the decoder's
+        ``differentiable_ood_head``): F.batch_norm in the mode ``self.norm.training`` says -- batch statistics and the running-statistics update
+        of nn.BatchNorm2d in training mode, the running statistics in eval mode -- then ReLU and the 1x1 convolution as a matmul.  x [B,C,H,W]
+        -> [B,out,H,W]."""
+        n = self.norm
+        if n.training and n.track_running_stats:
+            n.num_batches_tracked.add_(1)
+        y = F.relu(F.batch_norm(x, n.running_mean, n.running_var, n.weight, n.bias, n.training, n.momentum, n.eps))
+        return torch.einsum("oc,bchw->bohw", self.conv.weight.flatten(1), y) + self.conv.bias[None, :, None, None]
+
 
 @TRANSFORMER_DECODER_REGISTRY.register()
 class MultiScaleMaskedTransformerDecoder(nn.Module):
@@ -249,10 +260,17 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
     then the calls after layers 0 ... L-2 -- each with ``pred_logits`` and a dense ``pred_masks`` [B,Q,H/4,W/4] that carry a graph over the same
     ten head tensors and nothing else.  Decoding is untouched (under ``no_grad``, sparse intermediate heads, the attention masks and final
     outputs of inference); the differentiable evaluations are added behind it on the decoder-layer outputs it held at each head call, and
-    their values are the bits the inference forward returns with ``sparse_intermediate_heads = False``."""
+    their values are the bits the inference forward returns with ``sparse_intermediate_heads = False``.
+
+    ``differentiable_ood_head`` (attribute, default False; read only with ``differentiable_heads`` set and grad mode on, on a model with the
+    DenseHybrid head) is the DenseHybrid recipe's FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP_AND_OOD_PRED: ``out["ood_pred"]`` is then computed in plain
+    torch on the detached ``mask_features`` (``BNReluConv.forward_differentiable``) and carries a graph over the head's four parameters --
+    ``ood_pred.norm.{weight,bias}``, ``ood_pred.conv.{weight,bias}`` -- and nothing else; the batch norm runs in the mode ``ood_pred.norm.training``
+    says and updates its running statistics in training mode.  Without it ``ood_pred`` stays the inference kernel's output under ``no_grad``."""
 
     differentiable_heads = False
     deep_supervision = False
+    differentiable_ood_head = False
     # forward() accepts the pixel decoder's DeferredMaskFeatures in place of the mask-feature tensor (MaskFormerHead asks for one when this is set)
     takes_deferred_mask_features = True
 
@@ -460,8 +478,11 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
                    for a, b in zip(predictions_class, predictions_mask)]
         out = {"pred_logits": cls, "pred_masks": msk, "aux_outputs": aux}
         if self.ood_prediction:
-            with frozen():
-                out["ood_pred"] = self.ood_pred(mask_features)                       # reference :467-468
+            if differentiable and self.differentiable_ood_head:
+                out["ood_pred"] = self.ood_pred.forward_differentiable(mask_features.detach())
+            else:
+                with frozen():
+                    out["ood_pred"] = self.ood_pred(mask_features)                   # reference :467-468
         return out
 
     def _decode(self, x, mask_features):

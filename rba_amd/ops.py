@@ -223,23 +223,20 @@ def rba_reduce_up4(mask_lowres, cls_prob, crop_hw, want_sem_seg=False, want_argm
     return rba, sem, arg
 
 
-@_hip_op
-def rba_reduce_backward(mask_pred, cls_prob, grad_score, score="rba", need_mask=True, need_prob=True):
-    """K1 backward.  mask_pred [Q,h,w], cls_prob [Q,K] (rba_reduce's inputs), grad_score [h,w] = dL/d score ->
-    (grad_mask [Q,h,w] | None, grad_prob [Q,K] | None), the gradients of rba_reduce's score (criterion.py:449-463 under autograd).
-    Both are bitwise reproducible from launch to launch."""
+def _k1_backward_args(who, mask_pred, cls_prob, grad, grad_name, grad_shape, need_mask, need_prob):
+    """The argument block both backward forms of K1 share: mask_pred [Q,h,w], cls_prob [Q,K], the upstream gradient `grad` of shape
+    `grad_shape(K, h, w)`, at least one output -> (Q, K, h * w, workspace | None, its bytes, grad_mask | None, grad_prob | None)."""
     _chk(mask_pred, "mask_pred", dim=3)
     _chk(cls_prob, "cls_prob", dim=2)
-    _chk(grad_score, "grad_score", dim=2)
-    mode = _mode(score)
     Q, H, W = mask_pred.shape
     if cls_prob.shape[0] != Q:
         raise RbaHipError(f"cls_prob has {cls_prob.shape[0]} queries, mask_pred {Q}")
-    if tuple(grad_score.shape) != (H, W):
-        raise RbaHipError(f"grad_score must have shape {(H, W)}, got {tuple(grad_score.shape)}")
-    if not (need_mask or need_prob):
-        raise RbaHipError("rba_reduce_backward: at least one of need_mask / need_prob")
     K = cls_prob.shape[1]
+    _chk(grad, grad_name, dim=len(grad_shape(K, H, W)))
+    if tuple(grad.shape) != grad_shape(K, H, W):
+        raise RbaHipError(f"{grad_name} must have shape {grad_shape(K, H, W)}, got {tuple(grad.shape)}")
+    if not (need_mask or need_prob):
+        raise RbaHipError(f"{who}: at least one of need_mask / need_prob")
     dev = mask_pred.device
     ws, ws_bytes = None, 0
     if need_prob:
@@ -249,7 +246,29 @@ def rba_reduce_backward(mask_pred, cls_prob, grad_score, score="rba", need_mask=
         ws = _k1_bwd_workspace(dev, ws_bytes)
     grad_mask = torch.empty((Q, H, W), dtype=torch.float32, device=dev) if need_mask else None
     grad_prob = torch.empty((Q, K), dtype=torch.float32, device=dev) if need_prob else None
-    _launch("rba_reduce_bwd_f32", _p(mask_pred), _p(cls_prob), _p(grad_score), _p(grad_mask), _p(grad_prob), Q, K, H * W, mode, _p(ws), ws_bytes)
+    return Q, K, H * W, ws, ws_bytes, grad_mask, grad_prob
+
+
+@_hip_op
+def rba_reduce_backward(mask_pred, cls_prob, grad_score, score="rba", need_mask=True, need_prob=True):
+    """K1 backward.  mask_pred [Q,h,w], cls_prob [Q,K] (rba_reduce's inputs), grad_score [h,w] = dL/d score ->
+    (grad_mask [Q,h,w] | None, grad_prob [Q,K] | None), the gradients of rba_reduce's score (criterion.py:449-463 under autograd).
+    Both are bitwise reproducible from launch to launch."""
+    mode = _mode(score)
+    Q, K, HW, ws, ws_bytes, grad_mask, grad_prob = _k1_backward_args("rba_reduce_backward", mask_pred, cls_prob, grad_score, "grad_score",
+                                                                     lambda K, H, W: (H, W), need_mask, need_prob)
+    _launch("rba_reduce_bwd_f32", _p(mask_pred), _p(cls_prob), _p(grad_score), _p(grad_mask), _p(grad_prob), Q, K, HW, mode, _p(ws), ws_bytes)
+    return grad_mask, grad_prob
+
+
+@_hip_op
+def sem_seg_backward(mask_pred, cls_prob, grad_sem, need_mask=True, need_prob=True):
+    """The per-class adjoint of K1.  mask_pred [Q,h,w], cls_prob [Q,K] (rba_reduce's inputs), grad_sem [K,h,w] = dL/d sem_seg (rba_reduce's
+    ``want_sem_seg`` output, the class map einsum("qc,qhw->chw", cls_prob, sigmoid(mask_pred))) -> (grad_mask [Q,h,w] | None, grad_prob [Q,K] | None).
+    K1 backward's kernel with the per-class gradient loaded instead of derived from a score's; both are bitwise reproducible from launch to launch."""
+    Q, K, HW, ws, ws_bytes, grad_mask, grad_prob = _k1_backward_args("sem_seg_backward", mask_pred, cls_prob, grad_sem, "grad_sem",
+                                                                     lambda K, H, W: (K, H, W), need_mask, need_prob)
+    _launch("rba_sem_seg_bwd_f32", _p(mask_pred), _p(cls_prob), _p(grad_sem), _p(grad_mask), _p(grad_prob), Q, K, HW, _p(ws), ws_bytes)
     return grad_mask, grad_prob
 
 
@@ -585,6 +604,64 @@ def outlier_tail_backward(score, labels, stats, grad_loss, func, thr_in, thr_out
     _launch("rba_outlier_tail_bwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, f, float(thr_in), float(thr_out), _p(stats), _p(grad_loss),
             _p(grad))
     return grad
+
+
+def _dense_hybrid_loss_args(sem, ood, labels):
+    """The argument block of K10: sem fp32 contiguous [B,K,h,w] with 1 <= K <= 32, ood fp32 contiguous [B,2,h,w], labels int64 or uint8 contiguous
+    [B,H,W], every size >= 1 and B H W, B K h w < 2^31 -> (B, K, h, w, H, W, bytes per label)."""
+    _chk(sem, "sem", dim=4)
+    _chk(ood, "ood", dim=4)
+    _chk(labels, "labels", dtype=torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64, dim=3)
+    (B, K, h, w), (H, W) = sem.shape, labels.shape[1:]
+    if tuple(ood.shape) != (B, 2, h, w):
+        raise RbaHipError(f"ood must have shape {(B, 2, h, w)} (sem is {tuple(sem.shape)}), got {tuple(ood.shape)}")
+    if not 1 <= K <= 32:
+        raise RbaHipError(f"dense_hybrid_loss: 1 <= K <= 32 classes, got {K}")
+    if labels.shape[0] != B or min(B, h, w, H, W) < 1 or max(B * H * W, B * K * h * w) >= 1 << 31:
+        raise RbaHipError(f"dense_hybrid_loss: sem [B,K,h,w] and labels [B,H,W] of one B, all sizes >= 1, B H W and B K h w < 2^31; got "
+                          f"{tuple(sem.shape)} and {tuple(labels.shape)}")
+    return B, K, h, w, H, W, labels.element_size()
+
+
+def _dense_hybrid_loss_workspace(device, nbytes):
+    """dense_hybrid_loss's per-workgroup partial sums: per (device, stream) and grow-only like K9's; the kernel writes every word it later reads."""
+    return _stream_workspace("dense_hybrid_loss", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+
+
+@_hip_op
+def dense_hybrid_loss(sem, ood, labels, beta):
+    """K10.  The reference's DenseHybrid loss behind its class map (criterion.py:406-431): sem [B,K,h,w] (the class map at mask resolution) and ood
+    [B,2,h,w] (``ood_pred``) sampled at every pixel of labels [B,H,W] (int64 or uint8; < K: that class, 254: outlier, anything else ignored by the
+    segmentation term) as F.interpolate(align_corners=True) does, log_softmax / logsumexp, get_batch_avg's mean and the two nll_loss means ->
+    (losses [4] = (loss, loss_seg, loss_ood, loss_th), stats [8] = (S_seg, S_ood, S_th, S_x, n_seg, n_ood, B H W, m), lse [B,H,W] = logsumexp_k of
+    the sampled class map, for the backward).  No class pixel or no outlier pixel: NaN.  Nothing is read back to the host; every result is bitwise
+    reproducible from launch to launch."""
+    B, K, h, w, H, W, nb = _dense_hybrid_loss_args(sem, ood, labels)
+    dev = sem.device
+    n = ctypes.c_int64(0)
+    _lib.check(_query("rba_dense_hybrid_loss_workspace_f32", B, H, W, ctypes.addressof(n)), "rba_dense_hybrid_loss_workspace_f32")
+    ws = _dense_hybrid_loss_workspace(dev, int(n.value))
+    losses = torch.empty((4,), dtype=torch.float32, device=dev)
+    stats = torch.empty((8,), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    _launch("rba_dense_hybrid_loss_fwd_f32", _p(sem), _p(ood), _p(labels), nb, B, K, h, w, H, W, float(beta), _p(ws), _p(losses), _p(stats), _p(lse))
+    return losses, stats, lse
+
+
+@_hip_op
+def dense_hybrid_loss_backward(sem, ood, labels, stats, lse, grad_loss, beta):
+    """K10.  dense_hybrid_loss's inputs, its ``stats`` and ``lse``, and the upstream gradient of losses[0] as a one-element fp32 device tensor (read
+    on the device) -> (grad_sem [B,K,h,w], grad_ood [B,2,h,w]), bitwise reproducible from launch to launch; a pixel no label pixel samples gets 0."""
+    B, K, h, w, H, W, nb = _dense_hybrid_loss_args(sem, ood, labels)
+    _shaped(stats, "stats", (8,))
+    _shaped(lse, "lse", (B, H, W))
+    if _chk(grad_loss, "grad_loss").numel() != 1:
+        raise RbaHipError(f"grad_loss must have one element, got shape {tuple(grad_loss.shape)}")
+    grad_sem = torch.empty((B, K, h, w), dtype=torch.float32, device=sem.device)
+    grad_ood = torch.empty((B, 2, h, w), dtype=torch.float32, device=sem.device)
+    _launch("rba_dense_hybrid_loss_bwd_f32", _p(sem), _p(ood), _p(labels), nb, _p(lse), B, K, h, w, H, W, float(beta), _p(stats), _p(grad_loss),
+            _p(grad_sem), _p(grad_ood))
+    return grad_sem, grad_ood
 
 
 @_hip_op
