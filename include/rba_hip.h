@@ -40,6 +40,11 @@
  *   rba_outlier_tail_bwd_f32       means (criterion.py:474-518); autograd's backward of them
  *   rba_dense_hybrid_loss_fwd_f32 <- SetCriterion.densehybrid_loss behind its class map: the two F.interpolate(align_corners=True), log_softmax,
  *   rba_dense_hybrid_loss_bwd_f32    logsumexp, get_batch_avg and the two nll_loss (criterion.py:93-97, 406-431); autograd's backward of them
+ *   rba_gambler_loss_fwd_f32    <- SetCriterion.gambler_loss behind its class map: F.interpolate(align_corners=True), softmax, logsumexp,
+ *   rba_gambler_loss_bwd_f32       GaussianBlur(7, 1) of the squared reward, the masked log terms (criterion.py:337-388); autograd's backward
+ *   rba_gaussian_blur_planes_f32 / _adjoint_f32 <- that blur on B planes and autograd's backward of it
+ *   rba_score_reg_fwd_f32       <- SetCriterion.smoothness_loss / sparsity_loss behind their score map (criterion.py:270-279, 311-319);
+ *   rba_score_reg_bwd_f32          autograd's backward of them
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -307,6 +312,54 @@ int rba_dense_hybrid_loss_fwd_f32(const float* sem, const float* ood, const void
 int rba_dense_hybrid_loss_bwd_f32(const float* sem, const float* ood, const void* labels, int label_bytes, const float* lse, int B, int K, int h,
                                   int w, int H, int W, float beta, const float* stats, const float* grad_loss /* device, [1] */,
                                   float* grad_sem /* [B,K,h,w] */, float* grad_ood /* [B,2,h,w] */, void* stream);
+
+/* K11a.  SetCriterion.gambler_loss behind its class map (mask2former/modeling/criterion.py:337-388; docs/kernels/K11.md).  sem [B,K+1,h,w] = the
+ * class map einsum("bqc,bqhw->bchw", softmax(cls), sigmoid(mask)) WITH the no-object column: channel K is the reservation channel.  Every label
+ * pixel samples its K + 1 values as F.interpolate(mode="bilinear", align_corners=True) does (K9's tap arithmetic); the up-sampled map is never
+ * written.  labels [B,H,W] in K10's convention (label_bytes = 8: int64, 1: uint8; < K: an inlier pixel of that class, 254: outlier, anything
+ * else void).  Per pixel, x_k = the samples:
+ *   L_in = logsumexp_{k<K} x_k   L = logsumexp_{k<=K} x_k   p_k = exp(x_k - L)   reward r = L_in^2   R = GaussianBlur(7, sigma = 1)(r) per plane
+ *   res = p_K / R     inlier: t_in = log(p_label + res) (no clamp)     outlier: t_out = sum_{k<K} log(max(p_k + res, 1e-7))
+ *   losses [3] = (loss, S_in / n_in, [n_ood > 0] S_out / (n_ood K)),  loss = -(losses[1] + ood_reg losses[2]);  stats [4] = (S_in, S_out, n_in, n_ood)
+ * n_in == 0 gives NaN, the mean of nothing, as in the reference; the reference's `ood_mask.sum() > 0` is decided on the device.  `reward` and R are
+ * [B,H,W] maps (reward: scratch of the call; R: an output, kept for the backward); `workspace`: device memory owned by the caller, 4-byte aligned,
+ * at least rba_gambler_loss_workspace_f32's byte count; its contents on entry do not matter.  No float atomics, no host read, every output
+ * bitwise reproducible from launch to launch.
+ *
+ * rba_gambler_loss_bwd_f32: grad_sem [B,K+1,h,w] = *grad_loss d losses[0] / d sem, the gradient through the blurred reward included, from the
+ * forward's inputs, `stats` and R (*grad_loss and stats are read on the device).  grad_R and grad_reward are [B,H,W] scratch maps of the call
+ * (d / d R per pixel, then its pull-back through the adjoint of the reflect-padded blur).  Gather form as K10's backward: plain stores whatever
+ * the outputs held before, bitwise reproducible; a pixel no label pixel samples (H < h) gets 0.
+ * Every B, h, w >= 1 and H, W >= 4 (the blur's reflect padding of 3 needs a larger map) with B H W and B (K+1) h w < 2^31, B <= 65535,
+ * 1 <= K <= 31; anything else, another label_bytes or a NULL pointer returns hipErrorInvalidValue without a launch. */
+int rba_gambler_loss_workspace_f32(int B, int H, int W, int64_t* bytes);
+int rba_gambler_loss_fwd_f32(const float* sem, const void* labels, int label_bytes /* 1 or 8 */, int B, int K, int h, int w, int H, int W,
+                             float ood_reg, float* workspace, float* reward /* [B,H,W] scratch */, float* losses /* [3] */, float* stats /* [4] */,
+                             float* R /* [B,H,W] */, void* stream);
+int rba_gambler_loss_bwd_f32(const float* sem, const void* labels, int label_bytes, const float* R, int B, int K, int h, int w, int H, int W,
+                             float ood_reg, const float* stats, const float* grad_loss /* device, [1] */, float* grad_R /* [B,H,W] scratch */,
+                             float* grad_reward /* [B,H,W] scratch */, float* grad_sem /* [B,K+1,h,w] */, void* stream);
+
+/* rba_gaussian_blur_f32 on B planes [B,H,W] per launch (for B = 1: its very bits), and the adjoint of that linear map -- NOT the blur itself:
+ * within kernel_size / 2 pixels of a border the taps that the reflect padding folds back add.  grad_in = A^T grad_out in gather form, plain
+ * stores, bitwise reproducible.  Odd kernel_size <= 15, sigma > 0, H and W > kernel_size / 2, 1 <= B <= 65535, in != out. */
+int rba_gaussian_blur_planes_f32(const float* in, float* out, int B, int H, int W, int kernel_size, float sigma, void* stream);
+int rba_gaussian_blur_planes_adjoint_f32(const float* grad_out, float* grad_in, int B, int H, int W, int kernel_size, float sigma, void* stream);
+
+/* K11b.  SetCriterion.smoothness_loss and sparsity_loss behind their score map (criterion.py:270-279, 311-319; docs/kernels/K11.md).  score [B,h,w];
+ * labels [B,H,W] (label_bytes = 8: int64, 1: uint8; 1 = outlier) or NULL (no "outlier_masks": H and W are then unused but must be >= 1).
+ *   losses[0] = smoothness = 1/2 (sum_{y<h-1} (s[y+1,x] - s[y,x])^2 + sum_{x<w-1} (s[y,x+1] - s[y,x])^2)       (a sum, not a mean)
+ *   losses[1] = sparsity = sqrt(sum_{label=1} up(s)^2), up = the align_corners=True bilinear upsample (K9's taps); 0 without labels or outlier pixel
+ *   stats [2] = the two sums.  K9's partial / finish scheme: `workspace` as there (rba_score_reg_workspace_f32), bitwise reproducible, no host read.
+ * rba_score_reg_bwd_f32: grad_score [B,h,w] = *grad_smooth d smoothness / d score + *grad_sparse d sparsity / d score (either pointer may be NULL = 0,
+ * not both; read on the device), one thread per score pixel in K9's gather form; the sparsity part is 0 where the norm is 0 (torch.norm's backward).
+ * Every B, h, w, H, W >= 1 with B H W and B h w < 2^31. */
+int rba_score_reg_workspace_f32(int B, int h, int w, int H, int W, int64_t* bytes);
+int rba_score_reg_fwd_f32(const float* score, const void* labels /* or NULL */, int label_bytes, int B, int h, int w, int H, int W, float* workspace,
+                          float* losses /* [2] */, float* stats /* [2] */, void* stream);
+int rba_score_reg_bwd_f32(const float* score, const void* labels /* or NULL */, int label_bytes, int B, int h, int w, int H, int W,
+                          const float* stats, const float* grad_smooth /* device, [1] or NULL */, const float* grad_sparse /* device, [1] or NULL */,
+                          float* grad_score /* [B,h,w] */, void* stream);
 
 /* K5.  Swin (shifted-)window attention core over a token map, fusing zero-pad to a multiple of the window,
  * cyclic shift, window partition, q*scale @ k^T + relative-position bias (+ shift mask), softmax, @ v,

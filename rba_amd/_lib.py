@@ -52,6 +52,14 @@ SIGNATURES = {
     "rba_dense_hybrid_loss_workspace_f32": [_i, _i, _i, _vp],
     "rba_dense_hybrid_loss_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
     "rba_dense_hybrid_loss_bwd_f32": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
+    "rba_gambler_loss_workspace_f32": [_i, _i, _i, _vp],
+    "rba_gambler_loss_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rba_gambler_loss_bwd_f32": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rba_gaussian_blur_planes_f32": [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp],
+    "rba_gaussian_blur_planes_adjoint_f32": [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp],
+    "rba_score_reg_workspace_f32": [_i, _i, _i, _i, _i, _vp],
+    "rba_score_reg_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "rba_score_reg_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],

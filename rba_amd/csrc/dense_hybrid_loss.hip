@@ -26,37 +26,6 @@ constexpr int DH_THREADS = 256, DH_MAX_GROUPS = 2048, DH_WS = 8;    // workspace
 constexpr int DH_SPLIT = 16, DH_OWNERS = DH_THREADS / DH_SPLIT;     // backward: lanes per owner pixel, owner pixels per workgroup
 constexpr int DH_OUTLIER = 254;
 
-// the label as 0 .. 255: every int64 value outside [0, 255) is one more ignored value.  The dtype is a template parameter of the kernels
-template <int LB>
-__device__ __forceinline__ int dh_label(const void* __restrict__ labels, int64_t i) {
-  if constexpr (LB == 1) {
-    return (int)reinterpret_cast<const uint8_t*>(labels)[i];
-  } else {
-    const int64_t v = reinterpret_cast<const int64_t*>(labels)[i];
-    return v >= 0 && v < 255 ? (int)v : 255;
-  }
-}
-
-struct DhTaps {           // the four taps of a label pixel as offsets into an [h, w] plane, and its weights
-  int o00, o01, o10, o11;
-  float hy, ly, hx, lx;
-};
-
-__device__ __forceinline__ DhTaps dh_taps(const AcTap& ty, const AcTap& tx, int w) {
-  DhTaps t;
-  t.o00 = ty.i0 * w + tx.i0;
-  t.o01 = ty.i0 * w + tx.i1;
-  t.o10 = ty.i1 * w + tx.i0;
-  t.o11 = ty.i1 * w + tx.i1;
-  t.hy = ty.h, t.ly = ty.l, t.hx = tx.h, t.lx = tx.l;
-  return t;
-}
-
-// ATen's operation order (bilinear_ac.h: upsampled)
-__device__ __forceinline__ float dh_sample(const float* __restrict__ plane, const DhTaps& t) {
-  return t.hy * (t.hx * plane[t.o00] + t.lx * plane[t.o01]) + t.ly * (t.hx * plane[t.o10] + t.lx * plane[t.o11]);
-}
-
 int dh_groups(int64_t total) {
   const int64_t g = (total + DH_THREADS - 1) / DH_THREADS;
   return (int)(g < DH_MAX_GROUPS ? g : DH_MAX_GROUPS);
@@ -96,14 +65,14 @@ __global__ __launch_bounds__(DH_THREADS) void dh_partial_kernel(const float* __r
   float s_seg = 0.f, s_ood = 0.f, s_th = 0.f, s_x = 0.f;
   int n_seg = 0, n_ood = 0;
   for (uint32_t i = blockIdx.x * DH_THREADS + tid; i < end; i += stride) {
-    const int lab = dh_label<LB>(labels, i);
+    const int lab = ac_label<LB>(labels, i);
     const int b = (int)(i / HW), r = (int)(i - (uint32_t)b * HW), Y = r / W, X = r - Y * W;
-    const DhTaps t = dh_taps(tap_of(Y, sy, h), tap_of(X, sx, w), w);
+    const AcTaps4 t = ac_taps4(tap_of(Y, sy, h), tap_of(X, sx, w), w);
     const float* sp = sem + (int64_t)b * K * hw;
     float x[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
-      if (k < K) x[k] = dh_sample(sp + (int64_t)k * hw, t);
+      if (k < K) x[k] = ac_sample(sp + (int64_t)k * hw, t);
     float mx = x[0], sum_x = 0.f, x_lab = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
@@ -127,7 +96,7 @@ __global__ __launch_bounds__(DH_THREADS) void dh_partial_kernel(const float* __r
       ++n_ood;
     }
     const float* op = ood + (int64_t)b * 2 * hw;
-    const float o0 = dh_sample(op, t), o1 = dh_sample(op + hw, t), om = fmaxf(o0, o1);
+    const float o0 = ac_sample(op, t), o1 = ac_sample(op + hw, t), om = fmaxf(o0, o1);
     s_th += om + logf(expf(o0 - om) + expf(o1 - om)) - (lab == DH_OUTLIER ? o1 : o0);
   }
   const float v = dh_block_reduce(s_seg, s_ood, s_th, s_x, n_seg, n_ood, red);
@@ -170,22 +139,6 @@ __global__ __launch_bounds__(DH_THREADS) void dh_finish_kernel(const float* __re
   }
 }
 
-// the destination rows / columns [lo, hi] whose tap pair names source row / column p: contiguous, because tap_of's i0 never decreases with dst
-// and a destination names p exactly while i0 is p - 1 (with i1 = p) or p.  lo > hi: nobody samples p.
-__device__ __forceinline__ void dh_naming(int p, float scale, int in, int out, int& lo, int& hi) {
-  int a, b;
-  candidates(p, scale, out, a, b);
-  lo = b + 1;
-  hi = a - 1;
-  for (int d = a; d <= b; ++d) {
-    const AcTap t = tap_of(d, scale, in);
-    if (t.i0 == p || t.i1 == p) {
-      lo = d < lo ? d : lo;
-      hi = d;
-    }
-  }
-}
-
 template <int KMAX, int LB>
 __global__ __launch_bounds__(DH_THREADS) void dh_bwd_kernel(const float* __restrict__ sem, const float* __restrict__ ood,
                                                             const void* __restrict__ labels, const float* __restrict__ lse, int K, int h, int w, int H,
@@ -202,8 +155,8 @@ __global__ __launch_bounds__(DH_THREADS) void dh_bwd_kernel(const float* __restr
   // d loss / d (a pixel's term): the means' 1 / n
   const float c_seg = g / stats[4], c_ood = g * beta / stats[5], c_th = g * 10.0f * beta / stats[6];
   int Y0, Y1, X0, X1;
-  dh_naming(y, sy, h, H, Y0, Y1);
-  dh_naming(x, sx, w, W, X0, X1);
+  ac_naming(y, sy, h, H, Y0, Y1);
+  ac_naming(x, sx, w, W, X0, X1);
   const uint32_t nX = X1 >= X0 ? X1 - X0 + 1 : 0;
   const uint32_t n = live && Y1 >= Y0 ? (uint32_t)(Y1 - Y0 + 1) * nX : 0;      // <= H W < 2^31: c + 16 stays below 2^32
   const float* sp = sem + (int64_t)b * K * hw;
@@ -216,11 +169,11 @@ __global__ __launch_bounds__(DH_THREADS) void dh_bwd_kernel(const float* __restr
     const int Y = Y0 + (int)dy, X = X0 + (int)(c - dy * nX);
     const AcTap ty = tap_of(Y, sy, h), tx = tap_of(X, sx, w);
     const float wgt = tap_weight(ty, y) * tap_weight(tx, x);
-    const DhTaps t = dh_taps(ty, tx, w);
+    const AcTaps4 t = ac_taps4(ty, tx, w);
     const int64_t P = ((int64_t)b * H + Y) * W + X;
-    const int lab = dh_label<LB>(labels, P);
+    const int lab = ac_label<LB>(labels, P);
     const bool out = lab == DH_OUTLIER;
-    const float o0 = dh_sample(op, t), o1 = dh_sample(op + hw, t), om = fmaxf(o0, o1);
+    const float o0 = ac_sample(op, t), o1 = ac_sample(op + hw, t), om = fmaxf(o0, o1);
     const float e0 = expf(o0 - om), e1 = expf(o1 - om), es = e0 + e1;
     a0 = fmaf(wgt, e0 / es - (out ? 0.f : 1.0f), a0);
     a1 = fmaf(wgt, e1 / es - (out ? 1.0f : 0.f), a1);
@@ -228,7 +181,7 @@ __global__ __launch_bounds__(DH_THREADS) void dh_bwd_kernel(const float* __restr
       const float cw = wgt * (out ? c_ood : c_seg), L = lse[P];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k)
-        if (k < K) acc[k] = fmaf(cw, expf(dh_sample(sp + (int64_t)k * hw, t) - L) - (k == lab ? 1.0f : 0.f), acc[k]);
+        if (k < K) acc[k] = fmaf(cw, expf(ac_sample(sp + (int64_t)k * hw, t) - L) - (k == lab ? 1.0f : 0.f), acc[k]);
     }
   }
   // the 16 lanes of an owner, a fixed xor tree (every lane of the wave is here)

@@ -18,8 +18,15 @@ maskformer_model.py:166-169): the class map ``einsum("bqc,bqhw->bchw")`` is K1's
 ``SemSegFunction`` (backward: K1's per-class adjoint, ``ops.sem_seg_backward``), and everything behind it -- the two ``align_corners=True``
 upsamples to the labels' size, log_softmax, logsumexp, get_batch_avg and the two nll_loss -- is K10 (``ops.dense_hybrid_loss`` /
 ``ops.dense_hybrid_loss_backward`` behind ``DenseHybridLossFunction``); the up-sampled maps never exist.  ``SetCriterion`` does not take
-"densehybrid": the function is called directly.  The gambler, smoothness and sparsity losses, data mappers and the trainer are not part of
-this library.
+"densehybrid": the function is called directly.
+
+``gambler_loss``, ``smoothness_loss`` and ``sparsity_loss`` (criterion.py:245-388), with ``outlier_loss`` the loss list of the PEBAL fine-tune
+recipe (maskformer_model.py:164-175): the gambler loss behind its (K+1)-channel class map -- the upsample, softmax, the squared-logsumexp
+reward and its Gaussian blur (through which the gradient flows), the masked log terms and the host-side "any outlier pixel" branch -- is K11a
+(``ops.gambler_loss`` / ``ops.gambler_loss_backward`` behind ``GamblerLossFunction``); the two regularisers behind K1's score map are K11b
+(``ops.score_reg`` / ``ops.score_reg_backward`` behind ``ScoreRegFunction``).  ``pebal_criterion_from_cfg`` builds the recipe's whole criterion
+(``PebalCriterion``: no matcher -- these losses ignore its indices); ``SetCriterion`` does not take the three names.  Data mappers and the
+trainer are not part of this library.
 """
 import torch
 import torch.nn.functional as F
@@ -95,20 +102,22 @@ def _score_mode(target, score_norm):
 
 
 def outlier_loss(outputs, targets, *, target="nls", score_norm="tanh", func="squared_hinge", inlier_upper_threshold=-1.0,
-                 outlier_lower_threshold=-0.1):
+                 outlier_lower_threshold=-0.1, score=None):
     """``SetCriterion.outlier_loss`` (criterion.py:435-553; the matcher's ``indices`` and ``num_masks`` are unused there and absent here).
     outputs["pred_logits"] [B,Q,K+1], outputs["pred_masks"] [B,Q,h,w]; targets[i]["outlier_masks"] [H,W] with 1 = outlier, 0 = inlier,
     anything else ignored -> {"outlier_loss": scalar}.  Kept from the reference: without an outlier pixel the inlier term is not halved
     (:483-487), and an empty inlier set gives NaN (the mean of nothing).  Not built (ValueError): target "softmax_entropy" / "sum_entropy",
-    score_norm "sigmoid", func "kl"."""
+    score_norm "sigmoid", func "kl".  ``score`` [B,h,w]: the K1 score of this (target, score_norm), computed by the caller (``k1_score``) and shared
+    with other losses; None = computed here."""
     mode = _score_mode(target, score_norm)
     if func not in FUNCS:
         raise ValueError(f"outlier_loss: func {func!r} is not built (built: {list(FUNCS)})")
     labels = torch.stack([t["outlier_masks"] for t in targets])                      # [B,H,W]
     if labels.dtype not in (torch.int64, torch.uint8):
         labels = torch.where(labels == 0, 0, torch.where(labels == 1, 1, 255)).to(torch.uint8)      # on the device, nothing read back
-    cls_prob = F.softmax(outputs["pred_logits"], dim=-1)[..., :-1]
-    score = RbaScoreFunction.apply(outputs["pred_masks"], cls_prob, mode)            # [B,h,w]
+    if score is None:
+        cls_prob = F.softmax(outputs["pred_logits"], dim=-1)[..., :-1]
+        score = RbaScoreFunction.apply(outputs["pred_masks"], cls_prob, mode)        # [B,h,w]
     return {"outlier_loss": OutlierTailFunction.apply(score, labels, func, inlier_upper_threshold, outlier_lower_threshold)}
 
 
@@ -211,6 +220,201 @@ def densehybrid_loss_from_cfg(cfg):
     model = cfg.get("MODEL", {})
     return functools.partial(densehybrid_loss, num_classes=int(model.get("SEM_SEG_HEAD", {}).get("NUM_CLASSES", 19)),
                              beta=float(model.get("MASK_FORMER", {}).get("DENSE_HYBRID_BETA", 0.03)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the PEBAL fine-tune losses (K11)
+class GamblerLossFunction(Function):
+    """``GamblerLossFunction.apply(sem [B,K+1,h,w], labels [B,H,W] int64 | uint8, ood_reg) -> loss`` (a scalar): ``ops.gambler_loss``
+    (losses[0], the very bits of a direct call), differentiable once with respect to ``sem`` through ``ops.gambler_loss_backward``.  Saved: the two
+    inputs, the sums and the [B,H,W] blurred reward.  No host synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, sem, labels, ood_reg):
+        sem, labels = sem.contiguous(), labels.contiguous()
+        losses, stats, R = ops.gambler_loss(sem, labels, ood_reg)
+        ctx.ood_reg = ood_reg
+        ctx.save_for_backward(sem, labels, stats, R)
+        return losses[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        sem, labels, stats, R = ctx.saved_tensors
+        return ops.gambler_loss_backward(sem, labels, stats, R, grad_loss.contiguous(), ctx.ood_reg), None, None
+
+
+class ScoreRegFunction(Function):
+    """``ScoreRegFunction.apply(score [B,h,w], labels [B,H,W] int64 | uint8 | None) -> (smoothness, sparsity)`` (two scalars): ``ops.score_reg``
+    (the very bits of a direct call), differentiable once with respect to ``score`` through ``ops.score_reg_backward``; the two upstream gradients
+    reach the kernel as two device scalars.  Saved: score, labels and the two sums.  No host synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, score, labels):
+        score = score.contiguous()
+        labels = None if labels is None else labels.contiguous()
+        losses, stats = ops.score_reg(score, labels)
+        ctx.has_labels = labels is not None
+        ctx.save_for_backward(*((score, stats, labels) if ctx.has_labels else (score, stats)))
+        return losses[0], losses[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_smoothness, grad_sparsity):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        score, stats = ctx.saved_tensors[:2]
+        labels = ctx.saved_tensors[2] if ctx.has_labels else None
+        return ops.score_reg_backward(score, labels, stats, grad_smoothness.contiguous(), grad_sparsity.contiguous()), None
+
+
+# SMOOTHNESS_SCORE -> K1 score mode (criterion.py:260-268; the third branch there tests another attribute and is not built)
+_SMOOTHNESS_SCORES = {"nls": "neg_logit_sum", "energy": "energy"}
+
+
+def k1_score(outputs, mode):
+    """The K1 score [B,h,w] of an outputs entry at the mask resolution (criterion.py:254-263, 449-465): ``mode`` is one of ``ops.SCORE_MODES``."""
+    return RbaScoreFunction.apply(outputs["pred_masks"], F.softmax(outputs["pred_logits"], dim=-1)[..., :-1], mode)
+
+
+def _smoothness_score(outputs, score, who):
+    if isinstance(score, torch.Tensor):
+        return score
+    if score not in _SMOOTHNESS_SCORES:
+        raise ValueError(f"{who}: score {score!r} is not built (built: {sorted(_SMOOTHNESS_SCORES)})")
+    return k1_score(outputs, _SMOOTHNESS_SCORES[score])
+
+
+def _outlier_plane(targets):
+    """targets[i]["outlier_masks"] stacked to [B,H,W] int64 | uint8 (another dtype: reduced on the device to 1 / 255), or None without that key"""
+    if "outlier_masks" not in targets[0]:
+        return None
+    labels = torch.stack([t["outlier_masks"] for t in targets])
+    if labels.dtype not in (torch.int64, torch.uint8):
+        labels = torch.where(labels == 1, 1, 255).to(torch.uint8)
+    return labels
+
+
+def smoothness_loss(outputs, targets, *, score="energy"):
+    """``SetCriterion.smoothness_loss`` (criterion.py:245-281; ``indices`` and ``num_masks`` are unused there and absent here; so are the targets).
+    ``score``: SMOOTHNESS_SCORE "energy" | "nls" (K1 at the mask resolution), or that score map [B,h,w] computed by the caller
+    -> {"smoothness_loss": half the sum of the squared forward differences along both axes}."""
+    s = _smoothness_score(outputs, score, "smoothness_loss")
+    return {"smoothness_loss": ScoreRegFunction.apply(s, None)[0]}
+
+
+def sparsity_loss(outputs, targets, *, score="energy"):
+    """``SetCriterion.sparsity_loss`` (criterion.py:283-321).  ``score`` as in ``smoothness_loss``; targets[i]["outlier_masks"] [H,W] with 1 =
+    outlier -> {"sparsity_loss": the 2-norm of the ``align_corners=True`` upsampled score over the outlier pixels}; 0 (with a zero gradient)
+    without an outlier pixel or without that key."""
+    s = _smoothness_score(outputs, score, "sparsity_loss")
+    return {"sparsity_loss": ScoreRegFunction.apply(s, _outlier_plane(targets))[1]}
+
+
+def gambler_loss(outputs, targets, *, num_classes, ood_reg=0.1):
+    """``SetCriterion.gambler_loss`` (criterion.py:323-388; ``indices`` and ``num_masks`` are unused there and absent here).
+    outputs["pred_logits"] [B,Q,K+1], outputs["pred_masks"] [B,Q,h,w]; targets[i]["outlier_masks"] [H,W] (1 = outlier, 255 = void, anything else
+    inlier) and targets[i]["sem_seg"] [H,W] (the inlier pixels' classes) -> {"gambler_loss": scalar}.  The one label plane is built on the
+    device -- outlier 1 -> 254, 255 -> 255, otherwise the ``sem_seg`` value if < K, else 255 -- and neither target is written (the reference
+    relabels both in place).  One departure: an inlier pixel whose label is not a class is an index error in the reference and void here, as in
+    ``densehybrid_loss``.  Kept from the reference: without an inlier pixel the loss is NaN.  ``self.pebal_reward`` there is dead code (the
+    reward map always has elements) and is not built."""
+    K = outputs["pred_logits"].shape[-1] - 1
+    if K != num_classes:
+        raise ValueError(f"gambler_loss: pred_logits has {K} classes (and no-object), num_classes is {num_classes}")
+    om = torch.stack([t["outlier_masks"] for t in targets])                          # [B,H,W]
+    ss = torch.stack([t["sem_seg"] for t in targets])
+    labels = torch.where(om == 1, 254, torch.where((om != 255) & (ss >= 0) & (ss < K), ss, 255)).to(torch.uint8)      # nothing read back
+    sem = SemSegFunction.apply(outputs["pred_masks"], F.softmax(outputs["pred_logits"], dim=-1))      # [B,K+1,h,w]: the no-object column stays (:327)
+    return {"gambler_loss": GamblerLossFunction.apply(sem, labels, float(ood_reg))}
+
+
+class PebalCriterion(torch.nn.Module):
+    """The criterion of the PEBAL fine-tune recipe: the loss list maskformer_model.py:164-175 produces with GAMBLER_LOSS -- "gambler", then
+    "smoothness", "sparsity" and "outlier" as configured -- over the final outputs and every ``aux_outputs`` entry i (key suffix ``_{i}``), as
+    ``SetCriterion.forward`` does.  No matcher is called: these four losses ignore its indices.  The K1 score of an entry is computed once and
+    shared by the losses that select the same K1 mode (the recipe: energy for all three).  ``outlier`` = the keyword settings of
+    ``outlier_loss``."""
+
+    def __init__(self, num_classes, weight_dict, losses, ood_reg=0.1, smoothness_score="energy", **outlier):
+        super().__init__()
+        for name in losses:
+            if name not in ("gambler", "smoothness", "sparsity", "outlier"):
+                raise ValueError(f"PebalCriterion: loss {name!r} is not one of gambler, smoothness, sparsity, outlier")
+        if smoothness_score not in _SMOOTHNESS_SCORES:
+            raise ValueError(f"PebalCriterion: smoothness score {smoothness_score!r} is not built (built: {sorted(_SMOOTHNESS_SCORES)})")
+        unknown = set(outlier) - {"target", "score_norm", "func", "inlier_upper_threshold", "outlier_lower_threshold"}
+        if unknown:
+            raise TypeError(f"PebalCriterion: unknown outlier settings {sorted(unknown)}")
+        self.num_classes, self.weight_dict, self.losses, self.ood_reg = num_classes, dict(weight_dict), list(losses), float(ood_reg)
+        self.smoothness_score, self.outlier = smoothness_score, dict(outlier)
+
+    def _entry(self, outputs, targets):
+        scores = {}                                          # K1 mode -> score map of this entry
+
+        def score(mode):
+            if mode not in scores:
+                scores[mode] = k1_score(outputs, mode)
+            return scores[mode]
+
+        losses = {}
+        reg = [name for name in self.losses if name in ("smoothness", "sparsity")]
+        if reg:                                              # one K11b call serves both regularisers
+            labels = _outlier_plane(targets) if "sparsity" in reg else None
+            smooth, sparse = ScoreRegFunction.apply(score(_SMOOTHNESS_SCORES[self.smoothness_score]), labels)
+        for name in self.losses:
+            if name == "gambler":
+                losses.update(gambler_loss(outputs, targets, num_classes=self.num_classes, ood_reg=self.ood_reg))
+            elif name == "smoothness":
+                losses["smoothness_loss"] = smooth
+            elif name == "sparsity":
+                losses["sparsity_loss"] = sparse
+            else:
+                mode = _score_mode(self.outlier.get("target", "nls"), self.outlier.get("score_norm", "tanh"))
+                losses.update(outlier_loss(outputs, targets, score=score(mode), **self.outlier))
+        return losses
+
+    def forward(self, outputs, targets):
+        final = {k: v for k, v in outputs.items() if k != "aux_outputs"}
+        losses = self._entry(final, targets)
+        for i, aux in enumerate(outputs.get("aux_outputs", ())):
+            losses.update({f"{k}_{i}": v for k, v in self._entry(aux, targets).items()})
+        return losses
+
+    def weighted(self, losses):
+        """maskformer_model.py:283-288: every loss times its weight; a loss without a weight is dropped"""
+        return {k: v * self.weight_dict[k] for k, v in losses.items() if k in self.weight_dict}
+
+
+def pebal_criterion_from_cfg(cfg):
+    """The criterion the PEBAL recipe's config selects (maskformer_model.py:112-195 with GAMBLER_LOSS): ``PebalCriterion`` with the loss list,
+    weight_dict (with the ``_{i}`` copies of DEEP_SUPERVISION), PEBAL_OOD_REG, SMOOTHNESS_SCORE and, with OUTLIER_SUPERVISION,
+    ``outlier_loss_from_cfg``'s settings.  GAMBLER_LOSS unset, DENSE_HYBRID_LOSS beside it (the reference then drops the gambler loss), or a
+    score that is not built raises ValueError here."""
+    model = cfg.get("MODEL", {})
+    mf = model.get("MASK_FORMER", {})
+    v = {k: mf.get(k, d) for k, d in _CRITERION_DEFAULTS.items()}
+    if not v["GAMBLER_LOSS"]:
+        raise ValueError("pebal_criterion_from_cfg: GAMBLER_LOSS is not set; criterion_from_cfg builds the other recipes")
+    if v["DENSE_HYBRID_LOSS"]:
+        raise ValueError("pebal_criterion_from_cfg: DENSE_HYBRID_LOSS beside GAMBLER_LOSS selects the densehybrid recipe (densehybrid_loss_from_cfg)")
+    weight_dict = {"loss_ce": v["CLASS_WEIGHT"], "loss_mask": v["MASK_WEIGHT"], "loss_dice": v["DICE_WEIGHT"], "smoothness_loss": v["SMOOTHNESS_WEIGHT"],
+                   "sparsity_loss": v["SPARSITY_WEIGHT"], "outlier_loss": v["OUTLIER_WEIGHT"], "gambler_loss": v["GAMBLER_WEIGHT"],
+                   "densehybrid_loss": v["DENSE_HYBRID_WEIGHT"]}
+    if v["DEEP_SUPERVISION"]:
+        weight_dict.update({f"{k}_{i}": w for i in range(int(v["DEC_LAYERS"]) - 1) for k, w in list(weight_dict.items())})
+    losses = ["gambler"]
+    if v["SMOOTHNESS_LOSS"]:
+        losses.append("smoothness")
+    if v["SPARSITY_LOSS"]:
+        losses.append("sparsity")
+    outlier = {}
+    if v["OUTLIER_SUPERVISION"]:
+        losses.append("outlier")
+        outlier = outlier_loss_from_cfg(cfg).keywords
+    return PebalCriterion(int(model.get("SEM_SEG_HEAD", {}).get("NUM_CLASSES", 19)), weight_dict, losses, float(mf.get("PEBAL_OOD_REG", 0.1)),
+                          str(mf.get("SMOOTHNESS_SCORE", "energy")), **outlier)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the point-sampled mask losses (K8)

@@ -664,6 +664,149 @@ def dense_hybrid_loss_backward(sem, ood, labels, stats, lse, grad_loss, beta):
     return grad_sem, grad_ood
 
 
+def _label_dtype(labels):
+    return torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64
+
+
+def _one_element(t, name):
+    if _chk(t, name).numel() != 1:
+        raise RbaHipError(f"{name} must have one element, got shape {tuple(t.shape)}")
+    return t
+
+
+def _gambler_loss_args(sem, labels):
+    """The argument block of K11a: sem fp32 contiguous [B,K+1,h,w] with 2 <= K + 1 <= 32, labels int64 or uint8 contiguous [B,H,W] with H, W >= 4
+    (the blur's reflect padding), every other size >= 1, B <= 65535 and B H W, B (K+1) h w < 2^31 -> (B, K, h, w, H, W, bytes per label)."""
+    _chk(sem, "sem", dim=4)
+    _chk(labels, "labels", dtype=_label_dtype(labels), dim=3)
+    (B, K1, h, w), (H, W) = sem.shape, labels.shape[1:]
+    if not 2 <= K1 <= 32:
+        raise RbaHipError(f"gambler_loss: 2 <= K + 1 <= 32 channels (the classes and the reservation channel), got {K1}")
+    if labels.shape[0] != B or min(B, h, w) < 1 or min(H, W) < 4 or B > 65535 or max(B * H * W, B * K1 * h * w) >= 1 << 31:
+        raise RbaHipError(f"gambler_loss: sem [B,K+1,h,w] and labels [B,H,W] of one B <= 65535, H and W >= 4, all other sizes >= 1, B H W and "
+                          f"B (K+1) h w < 2^31; got {tuple(sem.shape)} and {tuple(labels.shape)}")
+    return B, K1 - 1, h, w, H, W, labels.element_size()
+
+
+@_hip_op
+def gambler_loss(sem, labels, ood_reg=0.1):
+    """K11a.  The reference's gambler loss behind its class map (criterion.py:337-388): sem [B,K+1,h,w] (the class map at mask resolution WITH the
+    no-object column: channel K is the reservation channel) sampled at every pixel of labels [B,H,W] (int64 or uint8; < K: an inlier pixel of
+    that class, 254: outlier, anything else void) as F.interpolate(align_corners=True) does, softmax, the squared logsumexp reward blurred by
+    GaussianBlur(7, sigma=1), the log terms and their means -> (losses [3] = (loss, inlier mean, outlier mean), stats [4] = (S_in, S_out, n_in,
+    n_ood), R [B,H,W] = the blurred reward, for the backward).  No inlier pixel: NaN; no outlier pixel: the outlier mean is 0.  Nothing is read
+    back to the host; every result is bitwise reproducible from launch to launch."""
+    B, K, h, w, H, W, nb = _gambler_loss_args(sem, labels)
+    dev = sem.device
+    n = ctypes.c_int64(0)
+    _lib.check(_query("rba_gambler_loss_workspace_f32", B, H, W, ctypes.addressof(n)), "rba_gambler_loss_workspace_f32")
+    ws = _stream_workspace("gambler_loss", dev, max(int(n.value) // 4, 1), torch.empty, torch.float32)
+    losses = torch.empty((3,), dtype=torch.float32, device=dev)
+    stats = torch.empty((4,), dtype=torch.float32, device=dev)
+    reward = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    R = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    _launch("rba_gambler_loss_fwd_f32", _p(sem), _p(labels), nb, B, K, h, w, H, W, float(ood_reg), _p(ws), _p(reward), _p(losses), _p(stats), _p(R))
+    return losses, stats, R
+
+
+@_hip_op
+def gambler_loss_backward(sem, labels, stats, R, grad_loss, ood_reg=0.1):
+    """K11a.  gambler_loss's inputs, its ``stats`` and ``R``, and the upstream gradient of losses[0] as a one-element fp32 device tensor (read on
+    the device) -> grad_sem [B,K+1,h,w], the gradient through the blurred reward included; bitwise reproducible from launch to launch; a pixel no
+    label pixel samples gets 0."""
+    B, K, h, w, H, W, nb = _gambler_loss_args(sem, labels)
+    _shaped(stats, "stats", (4,))
+    _shaped(R, "R", (B, H, W))
+    _one_element(grad_loss, "grad_loss")
+    dev = sem.device
+    grad_R = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    grad_reward = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    grad_sem = torch.empty((B, K + 1, h, w), dtype=torch.float32, device=dev)
+    _launch("rba_gambler_loss_bwd_f32", _p(sem), _p(labels), nb, _p(R), B, K, h, w, H, W, float(ood_reg), _p(stats), _p(grad_loss), _p(grad_R),
+            _p(grad_reward), _p(grad_sem))
+    return grad_sem
+
+
+def _blur_planes_args(x, name, kernel_size, sigma):
+    """x fp32 contiguous [B,H,W], 1 <= B <= 65535, an odd kernel_size <= 15, sigma > 0, H and W > kernel_size // 2 -> (B, H, W)"""
+    _chk(x, name, dim=3)
+    B, H, W = x.shape
+    if (kernel_size % 2 == 0 or not 1 <= kernel_size <= 15 or sigma <= 0 or not 1 <= B <= 65535 or min(H, W) <= kernel_size // 2
+            or B * H * W >= 1 << 31):
+        raise RbaHipError(f"gaussian_blur_planes needs [B,H,W] planes with 1 <= B <= 65535, an odd kernel_size <= 15, sigma > 0 and planes larger "
+                          f"than the padding; got {tuple(x.shape)}, kernel_size {kernel_size}, sigma {sigma}")
+    return B, H, W
+
+
+@_hip_op
+def gaussian_blur_planes(planes, kernel_size=7, sigma=1.0):
+    """transforms.GaussianBlur(kernel_size, sigma) of each of the B planes [B,H,W] (reflect padding) in one launch; for B = 1 the bits of
+    ``gaussian_blur``."""
+    B, H, W = _blur_planes_args(planes, "planes", kernel_size, sigma)
+    out = torch.empty_like(planes)
+    _launch("rba_gaussian_blur_planes_f32", _p(planes), _p(out), B, H, W, int(kernel_size), float(sigma))
+    return out
+
+
+@_hip_op
+def gaussian_blur_planes_adjoint(grad_out, kernel_size=7, sigma=1.0):
+    """The adjoint of ``gaussian_blur_planes`` (autograd's backward of it): grad_out [B,H,W] -> grad_in [B,H,W].  Not the blur itself: near a
+    border the taps the reflect padding folds back add.  Bitwise reproducible."""
+    B, H, W = _blur_planes_args(grad_out, "grad_out", kernel_size, sigma)
+    grad_in = torch.empty_like(grad_out)
+    _launch("rba_gaussian_blur_planes_adjoint_f32", _p(grad_out), _p(grad_in), B, H, W, int(kernel_size), float(sigma))
+    return grad_in
+
+
+def _score_reg_args(score, labels):
+    """The argument block of K11b: score fp32 contiguous [B,h,w]; labels None, or int64 / uint8 contiguous [B,H,W]; every size >= 1 and B H W,
+    B h w < 2^31 -> (B, h, w, H, W, bytes per label); without labels H = W = 1."""
+    _chk(score, "score", dim=3)
+    B, h, w = score.shape
+    H, W, nb = 1, 1, 8
+    if labels is not None:
+        _chk(labels, "labels", dtype=_label_dtype(labels), dim=3)
+        H, W, nb = labels.shape[1], labels.shape[2], labels.element_size()
+        if labels.shape[0] != B:
+            raise RbaHipError(f"score_reg: score [B,h,w] and labels [B,H,W] of one B; got {tuple(score.shape)} and {tuple(labels.shape)}")
+    if min(B, h, w, H, W) < 1 or max(B * H * W, B * h * w) >= 1 << 31:
+        raise RbaHipError(f"score_reg: all sizes >= 1, B H W and B h w < 2^31; got {tuple(score.shape)} and {(B, H, W)}")
+    return B, h, w, H, W, nb
+
+
+@_hip_op
+def score_reg(score, labels=None):
+    """K11b.  The reference's smoothness and sparsity losses behind their score map (criterion.py:270-279, 311-319): score [B,h,w]; labels
+    [B,H,W] (int64 or uint8; 1 = outlier) or None -> (losses [2] = (smoothness = half the sum of the squared forward differences along both axes,
+    sparsity = the 2-norm of the align_corners=True upsampled score over the outlier pixels; 0 without labels or without an outlier pixel),
+    stats [2] = the two sums, for the backward).  Nothing is read back; bitwise reproducible from launch to launch."""
+    B, h, w, H, W, nb = _score_reg_args(score, labels)
+    dev = score.device
+    n = ctypes.c_int64(0)
+    _lib.check(_query("rba_score_reg_workspace_f32", B, h, w, H, W, ctypes.addressof(n)), "rba_score_reg_workspace_f32")
+    ws = _stream_workspace("score_reg", dev, max(int(n.value) // 4, 1), torch.empty, torch.float32)
+    losses = torch.empty((2,), dtype=torch.float32, device=dev)
+    stats = torch.empty((2,), dtype=torch.float32, device=dev)
+    _launch("rba_score_reg_fwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, _p(ws), _p(losses), _p(stats))
+    return losses, stats
+
+
+@_hip_op
+def score_reg_backward(score, labels, stats, grad_smoothness=None, grad_sparsity=None):
+    """K11b.  score_reg's inputs and ``stats``, and the two upstream gradients as one-element fp32 device tensors (one may be None = 0; they are
+    read on the device) -> grad_score [B,h,w], bitwise reproducible; the sparsity part is 0 where the norm is 0."""
+    B, h, w, H, W, nb = _score_reg_args(score, labels)
+    _shaped(stats, "stats", (2,))
+    if grad_smoothness is None and grad_sparsity is None:
+        raise RbaHipError("score_reg_backward: at least one of grad_smoothness / grad_sparsity")
+    for g, name in ((grad_smoothness, "grad_smoothness"), (grad_sparsity, "grad_sparsity")):
+        if g is not None:
+            _one_element(g, name)
+    grad = torch.empty((B, h, w), dtype=torch.float32, device=score.device)
+    _launch("rba_score_reg_bwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, _p(stats), _p(grad_smoothness), _p(grad_sparsity), _p(grad))
+    return grad
+
+
 @_hip_op
 def swin_bias_fragments(rel_bias, window_size):
     """[nH,N,N] gathered relative-position bias -> the MFMA-fragment-ordered copy K5 reads with coalesced loads."""
