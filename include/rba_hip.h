@@ -45,6 +45,10 @@
  *   rba_gaussian_blur_planes_f32 / _adjoint_f32 <- that blur on B planes and autograd's backward of it
  *   rba_score_reg_fwd_f32       <- SetCriterion.smoothness_loss / sparsity_loss behind their score map (criterion.py:270-279, 311-319);
  *   rba_score_reg_bwd_f32          autograd's backward of them
+ *   rba_tta_merge_f32           <- SemanticSegmentorWithTTA._inference_one_image behind the per-view forwards: sem_seg_postprocess, flip, +=, / n
+ *                                  (mask2former/test_time_augmentation.py:83-97, maskformer_model.py:330-332) + the score functions of K1
+ *   rba_resize_u8_pil_bilinear  <- Detectron2's ResizeTransform on a uint8 image = Pillow's Image.resize(BILINEAR), with HFlipTransform folded in
+ *                                  (DatasetMapperTTA; TEST.AUG of configs/cityscapes/semantic-segmentation/Base-Cityscapes-SemanticSegmentation.yaml)
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -645,6 +649,39 @@ int rba_token_linear_f32(const float* x, const float* x_add, const void* packed,
                          const float* ln_weight, const float* ln_bias, float ln_eps, float* out, int64_t M, int N, int K, int act,
                          void* stream);
 int rba_token_linear_multi_f32(const float* x, const rba_token_linear_problem* problems, int n_problems, int64_t M, int K, void* stream);
+
+/* K12a.  The multi-view merge of test-time augmentation (mask2former/test_time_augmentation.py:83-97 over the per-view sem_seg_postprocess of
+ * maskformer_model.py:330-332; docs/kernels/K12.md).  A views, 1 <= A <= RBA_TTA_MAX_VIEWS; view a is sem[a] [K, h[a], w[a]] (device pointer; the class map
+ * rba_reduce_up4_f32 writes for that view) and flip[a] != 0 when the view's image was flipped horizontally.  `views` itself is a HOST pointer, read
+ * before the call returns.  For every output pixel (y, x) of the H x W grid and every class k:
+ *   s_a[k]   = the align_corners=False bilinear sample of sem[a][k] at (y, flip[a] ? W - 1 - x : x), rba_resample_bilinear_f32's arithmetic (the
+ *              resized map flipped, not the source flipped)
+ *   mean[k]  = (s_0[k] + s_1[k] + ... + s_{A-1}[k]) / A        (added in ascending view order from s_0, one true division)
+ *   score, argmax = rba_reduce_f32's epilogue on mean (score_mode 0 | 1 | 2, first maximum)
+ * score [H,W] required; sem_seg [K,H,W] (the mean) and argmax [H,W] (int32) optional (NULL = not written).  Plain stores whatever the outputs held
+ * before, no atomics, no workspace: bitwise reproducible, and the score does not depend on which optional outputs are asked for.  1 <= K <= 32; every
+ * H, W, h[a], w[a] >= 1 with K H W and K h[a] w[a] < 2^31; anything else returns hipErrorInvalidValue without a launch. */
+#define RBA_TTA_MAX_VIEWS 16
+typedef struct {
+  const float* sem[RBA_TTA_MAX_VIEWS];
+  int h[RBA_TTA_MAX_VIEWS];
+  int w[RBA_TTA_MAX_VIEWS];
+  int flip[RBA_TTA_MAX_VIEWS];
+} rba_tta_views;
+int rba_tta_merge_f32(const rba_tta_views* views /* host */, int A, int K, int H, int W, int score_mode, float* score, float* sem_seg /* or NULL */,
+                      int32_t* argmax /* or NULL */, void* stream);
+
+/* K12b.  Pillow's Image.resize(BILINEAR) of a uint8 image (what Detectron2's ResizeTransform applies to the views of test-time augmentation), CHW in
+ * and CHW out, equal to Pillow in every byte: the horizontal pass, then the vertical pass on its rounded uint8 result, each
+ *   out = clip(((1 << 21) + sum_{j < n} kk[j] * pixel[lo + j]) >> 22, 0, 255)
+ * with one coefficient table per axis built by the caller in double as Pillow builds it (rba_amd.ops.pil_bilinear_coeffs): kx int32 [W][ksize_x],
+ * bx int32 [W][2] = (lo, n) with lo >= 0, 0 <= n <= ksize_x, lo + n <= w; ky, by likewise for the rows -- device pointers, trusted.  An axis whose
+ * size does not change is skipped and its tables may be NULL; with both axes unchanged the image is copied.  flip != 0: the result is stored
+ * flipped horizontally (column W - 1 - x).  tmp: [C,h,W] bytes of device memory, needed only when both axes change; its contents on entry do not
+ * matter.  in, out and tmp must not overlap.  C, h, w, H, W >= 1 with C h w, C h W and C H W < 2^31. */
+int rba_resize_u8_pil_bilinear(const uint8_t* in /* [C,h,w] */, uint8_t* out /* [C,H,W] */, uint8_t* tmp /* [C,h,W] or NULL */, int C, int h, int w,
+                               int H, int W, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y,
+                               int flip, void* stream);
 
 #ifdef __cplusplus
 }

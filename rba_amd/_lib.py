@@ -60,6 +60,8 @@ SIGNATURES = {
     "rba_score_reg_workspace_f32": [_i, _i, _i, _i, _i, _vp],
     "rba_score_reg_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "rba_score_reg_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "rba_tta_merge_f32": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "rba_resize_u8_pil_bilinear": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],
@@ -120,6 +122,15 @@ class TokenLinearProblem(ctypes.Structure):
     """rba_token_linear_problem of include/rba_hip.h"""
     _fields_ = [("x_add", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p),
                 ("N", ctypes.c_int), ("ld_out", ctypes.c_int), ("act", ctypes.c_int)]
+
+
+TTA_MAX_VIEWS = 16        # RBA_TTA_MAX_VIEWS
+
+
+class TtaViews(ctypes.Structure):
+    """rba_tta_views of include/rba_hip.h"""
+    _fields_ = [("sem", ctypes.c_void_p * TTA_MAX_VIEWS), ("h", ctypes.c_int * TTA_MAX_VIEWS), ("w", ctypes.c_int * TTA_MAX_VIEWS),
+                ("flip", ctypes.c_int * TTA_MAX_VIEWS)]
 
 
 EXPECTED_ABI = 191        # rba_hip_version() the argtypes above were written for (include/rba_hip.h)

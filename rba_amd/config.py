@@ -86,6 +86,8 @@ _DEFAULTS = {
                                  "SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE": False}},
     },
     "SOLVER": {"FORCE_REGION_PARTITION": False},
+    # detectron2/config/defaults.py TEST.AUG (rba_amd.test_time_augmentation); the Cityscapes base config sets [512 .. 1792], 4096, FLIP
+    "TEST": {"AUG": {"ENABLED": False, "MIN_SIZES": [400, 500, 600, 700, 800, 900, 1000, 1100, 1200], "MAX_SIZE": 4000, "FLIP": True}},
 }
 
 

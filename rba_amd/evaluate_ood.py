@@ -123,7 +123,23 @@ def build_parser():
     p.add_argument("--share_device", type=int, default=int(os.environ.get("RBA_EVAL_SHARE_DEVICE", "0")),
                    help="1: every rank uses device 0 and the metric exchange runs on gloo -- a plumbing test of the sharded evaluator on a "
                         "one-GPU box (RCCL refuses two ranks on one device), never a measurement")
+    p.add_argument("--tta", action="store_true",
+                   help="test-time augmentation: score every image through SemanticSegmentorWithTTA (the views of the checkpoint config's TEST.AUG: "
+                        "MIN_SIZES, MAX_SIZE, FLIP); also on when that config has TEST.AUG.ENABLED.  Runs the serial one-stream loop without "
+                        "graph replay, whatever --streams / --graph say")
     return p
+
+
+def with_tta(model, cfg, args):
+    """--tta, or TEST.AUG.ENABLED in the checkpoint's config: (the model wrapped in SemanticSegmentorWithTTA, args for the serial loop).  A wrapped
+    forward is a dozen forwards of different shapes and a merge: it is never captured into a per-image graph (GraphedScore would capture any score
+    function whose model is not a MaskFormer), so the loop runs on one stream with graphs off.  Otherwise (model, args) as they are."""
+    from .test_time_augmentation import SemanticSegmentorWithTTA, tta_enabled
+    if not (getattr(args, "tta", False) or tta_enabled(cfg)):
+        return model, args
+    serial = argparse.Namespace(**vars(args))
+    serial.streams, serial.graph = 1, 0
+    return SemanticSegmentorWithTTA(cfg, model), serial
 
 
 class GraphedScore:
@@ -440,10 +456,11 @@ def _evaluate_models(models, names, args, rank, world, device):
                         print("Model path does not exist, skipping")
                     continue
         model = get_model(os.path.join(exp, "config.yaml"), model_path, device=device)
+        model, run_args = with_tta(model, load_cfg(os.path.join(exp, "config.yaml")), args)
         results, timings = {}, {}
         for name in names:
             timings[name] = {}
-            results[name] = run_evaluations(model, get_dataset(name, args.datasets_folder), model_name, name, args, rank, world,
+            results[name] = run_evaluations(model, get_dataset(name, args.datasets_folder), model_name, name, run_args, rank, world,
                                             timing=timings[name])
         if rank == 0:
             if args.verbose:

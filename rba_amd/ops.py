@@ -288,6 +288,102 @@ def resample_bilinear(x, size, add=None):
     return out
 
 
+@_hip_op
+def tta_merge(views, flips, size, want_sem_seg=False, want_argmax=False, score="rba"):
+    """K12a, the multi-view merge of test-time augmentation (test_time_augmentation.py:83-97).  views: 1..16 class maps [K,h_a,w_a] (what
+    rba_reduce_up4(..., want_sem_seg=True) gives for each view), flips: one bool per view, size: the output (H, W) -> (score [H,W],
+    sem_seg [K,H,W] | None, argmax int32 [H,W] | None): every view resampled to (H, W) (align_corners=False), a flipped view read at column
+    W - 1 - x, the views added in order and divided once by their number; the score of that mean as K1 computes it.  No resized map exists."""
+    views, flips = list(views), [bool(f) for f in flips]
+    if not 1 <= len(views) <= _lib.TTA_MAX_VIEWS:
+        raise RbaHipError(f"tta_merge takes 1..{_lib.TTA_MAX_VIEWS} views, got {len(views)}")
+    if len(flips) != len(views):
+        raise RbaHipError(f"tta_merge: {len(views)} views but {len(flips)} flip flags")
+    for a, v in enumerate(views):
+        _chk(v, f"views[{a}]", dim=3)
+    K = views[0].shape[0]
+    if any(v.shape[0] != K for v in views):
+        raise RbaHipError(f"tta_merge: every view must have the same K, got {[v.shape[0] for v in views]}")
+    if not 1 <= K <= 32:
+        raise RbaHipError(f"tta_merge needs 1 <= K <= 32, got {K}")
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1 or any(v.shape[1] < 1 or v.shape[2] < 1 for v in views):
+        raise RbaHipError("tta_merge: empty view or output")
+    if K * H * W >= 1 << 31 or any(v.numel() >= 1 << 31 for v in views):
+        raise RbaHipError("tta_merge: K H W and every K h w must be below 2^31")
+    mode = _mode(score)
+    arg_ = _lib.TtaViews()
+    for a, v in enumerate(views):
+        arg_.sem[a], arg_.h[a], arg_.w[a], arg_.flip[a] = v.data_ptr(), v.shape[1], v.shape[2], int(flips[a])
+    dev = views[0].device
+    rba = torch.empty((H, W), dtype=torch.float32, device=dev)
+    sem = torch.empty((K, H, W), dtype=torch.float32, device=dev) if want_sem_seg else None
+    arg = torch.empty((H, W), dtype=torch.int32, device=dev) if want_argmax else None
+    _launch("rba_tta_merge_f32", ctypes.addressof(arg_), len(views), K, H, W, mode, _p(rba), _p(sem), _p(arg))
+    return rba, sem, arg
+
+
+def pil_bilinear_coeffs(n_in, n_out):
+    """Pillow's coefficient table of Image.resize(BILINEAR) for one axis of n_in -> n_out pixels (src/libImaging/Resample.c precompute_coeffs +
+    normalize_coeffs_8bpc), built in double as Pillow builds it -> (kk int32 [n_out, ksize], bounds int32 [n_out, 2] = (first pixel, count), ksize).
+    The triangle filter's support is max(n_in / n_out, 1): it widens when down-scaling.  Weights are summed left to right, as Pillow sums them."""
+    import numpy as np
+    n_in, n_out = int(n_in), int(n_out)
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                 # (int) truncates; the operands are >= 0 after the clamp ...
+    xmin = np.where(center - support + 0.5 < 0, 0, xmin)                            # ... and a negative one clamps to 0 either way
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+    j = np.arange(ksize, dtype=np.float64)[None, :]
+    x = (j + xmin[:, None] - center[:, None] + 0.5) * (1.0 / fs)
+    w = np.where(np.abs(x) < 1.0, 1.0 - np.abs(x), 0.0)
+    w = np.where(j < xmax[:, None], w, 0.0)
+    ww = np.zeros(n_out, dtype=np.float64)
+    for c in range(ksize):                                                          # Pillow's running sum, left to right
+        ww = ww + w[:, c]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    s = w * float(1 << 22)
+    kk = np.where(s < 0, (s - 0.5).astype(np.int64), (s + 0.5).astype(np.int64)).astype(np.int32)      # (int) truncates toward zero
+    bounds = np.stack([xmin, xmax], axis=1).astype(np.int32)
+    return np.ascontiguousarray(kk), np.ascontiguousarray(bounds), ksize
+
+
+_PIL_TABLES = {}          # (device index, n_in, n_out) -> (kk, bounds, ksize) on the device
+
+
+def _pil_tables(device, n_in, n_out):
+    """The device copy of one axis' table, uploaded once per (device, n_in, n_out): a TTA recipe has a dozen of them, a few hundred KB together"""
+    key = (device.index, int(n_in), int(n_out))
+    t = _PIL_TABLES.get(key)
+    if t is None:
+        if len(_PIL_TABLES) >= 256:
+            _PIL_TABLES.clear()
+        kk, bounds, ksize = pil_bilinear_coeffs(n_in, n_out)
+        t = _PIL_TABLES[key] = (torch.from_numpy(kk).to(device), torch.from_numpy(bounds).to(device), ksize)
+    return t
+
+
+@_hip_op
+def resize_u8_pil_bilinear(image, size, flip=False):
+    """K12b.  image uint8 [C,h,w] -> uint8 [C,H,W]: Pillow's Image.resize((W, H), BILINEAR) of the image, equal to Pillow in every byte (what
+    Detectron2's ResizeTransform gives a uint8 image), with ``flip`` the result flipped horizontally (HFlipTransform) in the same pass."""
+    _chk(image, "image", dtype=torch.uint8, dim=3)
+    C, h, w = (int(v) for v in image.shape)
+    H, W = int(size[0]), int(size[1])
+    if min(C, h, w, H, W) < 1 or max(C * h * w, C * h * W, C * H * W) >= 1 << 31:
+        raise RbaHipError("resize_u8_pil_bilinear needs a non-empty [C,h,w] image and size, each of C h w, C h W, C H W below 2^31")
+    dev = image.device
+    kx, bx, ksx = _pil_tables(dev, w, W) if w != W else (None, None, 0)
+    ky, by, ksy = _pil_tables(dev, h, H) if h != H else (None, None, 0)
+    out = torch.empty((C, H, W), dtype=torch.uint8, device=dev)
+    tmp = torch.empty((C, h, W), dtype=torch.uint8, device=dev) if w != W and h != H else None
+    _launch("rba_resize_u8_pil_bilinear", _p(image), _p(out), _p(tmp), C, h, w, H, W, _p(kx), _p(bx), ksx, _p(ky), _p(by), ksy, int(bool(flip)))
+    return out
+
+
 def _msda_args(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step, grad_output=None, backward=False):
     """The argument block of multi-scale deformable attention, forward and (``backward``: with grad_output) backward -> (dtype, N, S, M, D, L, Lq, P)."""
     # float or double, like the reference op (AT_DISPATCH_FLOATING_TYPES, ms_deform_attn_cuda.cu:69); all tensors of one type
