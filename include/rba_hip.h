@@ -49,6 +49,7 @@
  *                                  (mask2former/test_time_augmentation.py:83-97, maskformer_model.py:330-332) + the score functions of K1
  *   rba_resize_u8_pil_bilinear  <- Detectron2's ResizeTransform on a uint8 image = Pillow's Image.resize(BILINEAR), with HFlipTransform folded in
  *                                  (DatasetMapperTTA; TEST.AUG of configs/cityscapes/semantic-segmentation/Base-Cityscapes-SemanticSegmentation.yaml)
+ *   rba_confusion_accum         <- Detectron2's SemSegEvaluator.process: np.bincount((K + 1) * pred + gt) per image (train_net.py:96-121 builds it)
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -682,6 +683,20 @@ int rba_tta_merge_f32(const rba_tta_views* views /* host */, int A, int K, int H
 int rba_resize_u8_pil_bilinear(const uint8_t* in /* [C,h,w] */, uint8_t* out /* [C,H,W] */, uint8_t* tmp /* [C,h,W] or NULL */, int C, int h, int w,
                                int H, int W, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y,
                                int flip, void* stream);
+
+/* K13.  The confusion matrix of closed-set segmentation evaluation (Detectron2's SemSegEvaluator.process: np.bincount((K + 1) * pred + gt) on the host;
+ * docs/kernels/K13.md).  pred: n_pixels int32 predictions (K1's or K12a's argmax map); gt: n_pixels labels, uint8 (gt_bytes = 1) or int64 (gt_bytes = 8).
+ * Per pixel p:
+ *   g = gt[p];  with lut: g in 0..255 becomes lut[g], any other g is a bad label;  g == ignore_label (ignore_label >= 0 only) becomes K
+ *   0 <= g <= K and 0 <= pred[p] < K:  conf[pred[p] * (K+1) + g] += 1        (rows = predictions, columns = ground truth, column K = ignored)
+ *   otherwise nothing is added to conf and  bad[0] += 1 (g out of range, whatever pred[p] is)  or  bad[1] += 1 (only pred[p] out of range)
+ * conf [(K+1),(K+1)] and bad [2] are ACCUMULATED into (64-bit integer atomics: bitwise reproducible); the caller zeroes them once per evaluation.
+ * No workspace, no synchronisation, no read-back; capturable.  pred may be 4-byte and gt element-aligned only (a slice of a larger tensor): 16-byte loads
+ * are issued on 16-byte aligned addresses only.  1 <= K <= 255; 1 <= n_pixels <= 2^40; lut: 256 entries on the device or NULL; anything else returns
+ * hipErrorInvalidValue without a launch. */
+int rba_confusion_accum(const int32_t* pred, const void* gt, int gt_bytes /* 1 = uint8, 8 = int64 */, int64_t n_pixels, int K,
+                        int ignore_label /* < 0: none */, const uint8_t* lut /* 256 entries or NULL */, int64_t* conf /* [(K+1),(K+1)] */,
+                        int64_t* bad /* [2] */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,7 @@ SIGNATURES = {
     "rba_score_reg_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "rba_tta_merge_f32": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "rba_resize_u8_pil_bilinear": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
+    "rba_confusion_accum": [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],

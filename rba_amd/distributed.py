@@ -173,6 +173,27 @@ def pooled_ood_metrics(scores: torch.Tensor, labels: torch.Tensor) -> dict:
 
 
 @torch.no_grad()
+def pooled_confusion_flat(conf: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
+    """The closed-set evaluator's state summed over every rank, as it travels: conf int64 [(K+1), (K+1)] and bad int64 [2] flattened into ONE int64
+    tensor [(K+1)^2 + 2] and all_reduce(SUM)'d.  Every rank returns the same tensor; the inputs are left as they are.  Integer sums: exact, whatever the order."""
+    flat = torch.cat([conf.reshape(-1), bad.reshape(-1)]).to(torch.int64)
+    if not _skip_collective(_world()):
+        if flat.is_cuda and dist.get_backend() == "gloo":   # gloo has no device all_reduce: stage through the host (tests only)
+            host = flat.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM)
+            flat = host.to(flat.device)
+        else:
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+    return flat
+
+
+def pooled_confusion(conf: torch.Tensor, bad: torch.Tensor):
+    """pooled_confusion_flat split back -> (conf [(K+1), (K+1)], bad [2]), the sums over every rank"""
+    flat = pooled_confusion_flat(conf, bad)
+    return flat[:conf.numel()].reshape(conf.shape), flat[conf.numel():].reshape(bad.shape)
+
+
+@torch.no_grad()
 def histogram_ood_metrics(scores: torch.Tensor, labels: torch.Tensor, bits: int = 16) -> dict:
     """Approximate pooled metrics from 2 x 2^bits int64 histograms over the order-preserving integer key of the fp32
     score (top `bits` bits): one 1 MB all_reduce instead of gathering every pixel.  Scores sharing a bin are treated

@@ -384,6 +384,42 @@ def resize_u8_pil_bilinear(image, size, flip=False):
     return out
 
 
+@_hip_op
+def confusion_accumulate(pred, gt, num_classes, conf, bad, ignore_label=255, lut=None):
+    """K13.  pred int32 (an argmax map: rba_reduce / tta_merge ``want_argmax``), gt uint8 | int64 of the same shape, conf int64 [K+1, K+1], bad int64 [2]:
+    conf[pred, label] += 1 per pixel (Detectron2's SemSegEvaluator layout: rows = predictions, columns = ground truth, column K = ignored), where
+    label = gt, through ``lut`` (uint8 [256]; a gt outside 0..255 is a bad label) when given, ``ignore_label`` (None or < 0: none) -> K.  A label outside
+    0..K adds to bad[0], a prediction outside 0..K-1 (its label in range) to bad[1], neither to conf.  conf and bad are accumulated into -- zero them once
+    per evaluation; nothing is read back and nothing synchronises.  Pixels are evaluated at the label's size: a shape mismatch is the caller's error."""
+    K = int(num_classes)
+    if not 1 <= K <= 255:
+        raise RbaHipError(f"confusion_accumulate needs 1 <= num_classes <= 255, got {K}")
+    _chk(pred, "pred", dtype=torch.int32)
+    if not isinstance(gt, torch.Tensor) or gt.dtype not in (torch.uint8, torch.int64):
+        raise RbaHipError(f"gt must be a uint8 or int64 tensor, got {gt.dtype if isinstance(gt, torch.Tensor) else type(gt).__name__}")
+    _chk(gt, "gt", dtype=gt.dtype)
+    if pred.shape != gt.shape:
+        raise RbaHipError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have the same shape (evaluate at the label's size)")
+    if pred.numel() < 1:
+        raise RbaHipError("confusion_accumulate: empty maps")
+    _chk(conf, "conf", dtype=torch.int64, dim=2)
+    if tuple(conf.shape) != (K + 1, K + 1):
+        raise RbaHipError(f"conf must have shape {(K + 1, K + 1)}, got {tuple(conf.shape)}")
+    _chk(bad, "bad", dtype=torch.int64, dim=1)
+    if bad.numel() != 2:
+        raise RbaHipError(f"bad must have 2 elements, got {bad.numel()}")
+    if lut is not None:
+        _chk(lut, "lut", dtype=torch.uint8, dim=1)
+        if lut.numel() != 256:
+            raise RbaHipError(f"lut must have 256 entries, got {lut.numel()}")
+    ignore = -1 if ignore_label is None or int(ignore_label) < 0 else int(ignore_label)
+    _launch("rba_confusion_accum", _p(pred), _p(gt), gt.element_size(), pred.numel(), K, ignore, _p(lut), _p(conf), _p(bad))
+
+
+# K13's launch rule (csrc/confusion.hip), for tests that size a map to a number of sweeps of the capped grid
+CONFUSION_THREADS, CONFUSION_TILE, CONFUSION_GRID_CAP, CONFUSION_LDS_MAX_K = 256, 16, 512, 126
+
+
 def _msda_args(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step, grad_output=None, backward=False):
     """The argument block of multi-scale deformable attention, forward and (``backward``: with grad_output) backward -> (dtype, N, S, M, D, L, Lq, P)."""
     # float or double, like the reference op (AT_DISPATCH_FLOATING_TYPES, ms_deform_attn_cuda.cu:69); all tensors of one type

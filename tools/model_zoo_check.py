@@ -38,6 +38,9 @@ MODEL_ZOO = {
     "swin_l_1dl_rba_ood_map_coco": {"road_anomaly": {"aupr": 90.28, "fpr95": 4.92}, "fishyscapes_laf": {"aupr": 80.35, "fpr95": 4.58}},  # :142-150
 }
 DATASETS = ("road_anomaly", "fishyscapes_laf")
+# The "Cityscapes mIoU" column of MODEL_ZOO.md (:46, rows :54-72), in percent: the table of the Cityscapes-only models is the one that has it (the fine-tuned
+# models' tables list the fine-tuned component there instead).  Compared only with --cityscapes_root (python -m rba_amd.evaluate_semseg).
+MODEL_ZOO_MIOU = {"swin_b_1dl": 82.25, "swin_l_1dl": 82.65}
 
 
 def parse(argv=None):
@@ -53,6 +56,9 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1, help="> 1: the evaluator runs under torch.distributed.run, images sharded over the ranks, metrics pooled by RCCL")
     p.add_argument("--results-only", action="store_true", help="do not run the evaluator: compare the results.pkl files under --out_path")
     p.add_argument("--dry-run", action="store_true", help="list what would be evaluated and compared, then stop (needs no GPU)")
+    p.add_argument("--cityscapes_root", default=None, help="also run python -m rba_amd.evaluate_semseg on this Cityscapes folder (leftImg8bit/, gtFine/) and "
+                   "compare the val mIoU of every model that has a row in MODEL_ZOO_MIOU")
+    p.add_argument("--semseg-tta", action="store_true", help="with --cityscapes_root: multi-scale + flip inference (the checkpoint config's TEST.AUG)")
     p.add_argument("--evaluator-args", nargs=argparse.REMAINDER, default=[], help="everything after this flag goes to rba_amd.evaluate_ood verbatim")
     return p.parse_args(argv)
 
@@ -115,12 +121,46 @@ def compare(args, models):
     return rows, worst
 
 
+def run_semseg(args, models):
+    ev = ["--models_folder", args.models_folder, "--selected_models", *models, "--cityscapes_root", args.cityscapes_root, "--out_path", args.out_path,
+          *(["--tta"] if args.semseg_tta else [])]
+    if args.gpus > 1:
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+               "--master-port", str(29500 + os.getpid() % 2000), "-m", "rba_amd.evaluate_semseg", *ev]
+        env = dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""), HSA_ENABLE_IPC_MODE_LEGACY="0")
+        subprocess.run(cmd, check=True, cwd=REPO, env=env)
+    else:
+        from rba_amd import evaluate_semseg
+        evaluate_semseg.main(ev)
+
+
+def compare_semseg(args, models):
+    """rows as compare()'s, one per model with a published Cityscapes mIoU: (model, "cityscapes", "mIoU", published, measured | None, diff | None, ok), and
+    the protocols the sem_seg.json files say they were measured with"""
+    rows, worst, protocols = [], 0.0, set()
+    for m in models:
+        if m not in MODEL_ZOO_MIOU:
+            continue
+        pub, path = MODEL_ZOO_MIOU[m], os.path.join(args.out_path, m, "sem_seg.json")
+        if not os.path.exists(path):
+            rows.append((m, "cityscapes", "mIoU", pub, None, None, False))
+            continue
+        with open(path) as f:
+            res = json.load(f)
+        protocols.add("TTA (multi-scale + flip)" if res.get("tta") else "single scale")
+        got = float(res["sem_seg"]["mIoU"])
+        diff = got - pub
+        worst = max(worst, abs(diff))
+        rows.append((m, "cityscapes", "mIoU", pub, got, diff, abs(diff) <= args.tolerance + 1e-12))
+    return rows, worst, protocols
+
+
 def report(rows, tolerance, file=sys.stdout):
     name = {"aupr": "AP", "fpr95": "FPR95", "auroc": "AUROC"}
     print(f"{'model':34s} {'dataset':16s} {'metric':6s} {'published':>9s} {'measured':>10s} {'diff':>9s}  verdict (tolerance {tolerance} pp)", file=file)
     for m, ds, metric, pub, got, diff, ok in rows:
         if got is None:
-            print(f"{m:34s} {ds:16s} {name.get(metric, metric):6s} {pub:9.2f} {'-':>10s} {'-':>9s}  MISSING (no results.pkl entry)", file=file)
+            print(f"{m:34s} {ds:16s} {name.get(metric, metric):6s} {pub:9.2f} {'-':>10s} {'-':>9s}  MISSING (no {'sem_seg.json' if metric == 'mIoU' else 'results.pkl entry'})", file=file)
         else:
             three = "" if ok else ("  [inside 0.05 pp = three decimals of the fraction]" if abs(diff) <= 0.05 else "")
             print(f"{m:34s} {ds:16s} {name.get(metric, metric):6s} {pub:9.2f} {got:10.4f} {diff:+9.4f}  {'ok' if ok else 'DIFFERS'}{three}", file=file)
@@ -140,6 +180,14 @@ def main(argv=None):
     if not args.results_only and runnable:
         run_evaluator(args, runnable)
     rows, worst = compare(args, [m for m, _, _ in todo])
+    if args.cityscapes_root:
+        semseg = [m for m in runnable if m in MODEL_ZOO_MIOU]
+        if not args.results_only and semseg:
+            run_semseg(args, semseg)
+        rows_m, worst_m, protocols = compare_semseg(args, [m for m, _, _ in todo])
+        rows, worst = rows + rows_m, max(worst, worst_m)
+        print(f"[model_zoo_check] Cityscapes mIoU measured with: {', '.join(sorted(protocols)) or 'nothing (no sem_seg.json)'} -- MODEL_ZOO.md does not say "
+              "whether its column is single scale or TTA")
     report(rows, args.tolerance)
     bad = [r for r in rows if not r[6]]
     print(f"[model_zoo_check] {len(rows) - len(bad)} of {len(rows)} published numbers reproduced within {args.tolerance} percentage points; "
