@@ -50,6 +50,8 @@
  *   rba_resize_u8_pil_bilinear  <- Detectron2's ResizeTransform on a uint8 image = Pillow's Image.resize(BILINEAR), with HFlipTransform folded in
  *                                  (DatasetMapperTTA; TEST.AUG of configs/cityscapes/semantic-segmentation/Base-Cityscapes-SemanticSegmentation.yaml)
  *   rba_confusion_accum         <- Detectron2's SemSegEvaluator.process: np.bincount((K + 1) * pred + gt) per image (train_net.py:96-121 builds it)
+ *   rba_train_view_u8           <- MaskFormerSemanticCocoMixDatasetMapper.__call__ behind the decode: mix_object, ResizeShortestEdge, RandomCrop,
+ *                                  ColorAugSSDTransform, RandomFlip, the pad and the outlier mask (mask_former_semantic_coco_mix_dataset_mapper.py)
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -697,6 +699,60 @@ int rba_resize_u8_pil_bilinear(const uint8_t* in /* [C,h,w] */, uint8_t* out /* 
 int rba_confusion_accum(const int32_t* pred, const void* gt, int gt_bytes /* 1 = uint8, 8 = int64 */, int64_t n_pixels, int K,
                         int ignore_label /* < 0: none */, const uint8_t* lut /* 256 entries or NULL */, int64_t* conf /* [(K+1),(K+1)] */,
                         int64_t* bad /* [2] */, void* stream);
+
+/* K14.  The training view of the COCO-mix fine-tune mapper (mask_former_semantic_coco_mix_dataset_mapper.py over Detectron2's ResizeShortestEdge,
+ * RandomCrop, ColorAugSSDTransform, RandomFlip; docs/kernels/K14.md): one launch writes the finished view from the source frame, every element equal
+ * to the host composition.  All pointers are device pointers; the struct itself is read on the host.
+ *   source read at (r, c): obj / ood_label where (r - py, c - px) lies in the [bh, bw] box and objmask == ood_label there, else img / lab (lab through
+ *     lut when lut is given) -- the reference's mix_object folded into the fetch; bh = bw = 0: no paste.
+ *   image (y, x), channel c, with Y = y0 + y, X = x0 + (flip ? cw - 1 - x : x): Pillow's horizontal pass first, the vertical pass on its rounded
+ *     uint8 result (K12b's arithmetic and tables: kx [new_w][ksize_x], bx [new_w][2], ky [new_h][ksize_y], by [new_h][2], trusted; tables whose
+ *     bounds grow with the index, as Pillow's do); an axis whose size does not change has no pass and its tables may be NULL.  Then, with
+ *     color.enabled, ColorAugSSDTransform(img_format = "RGB") on the pixel's three bytes: brightness; with `order` contrast, saturation, hue, else
+ *     saturation, hue, contrast; a leg that is off is skipped.  convert(p, alpha, beta) = uint8(trunc(clip(fl(fl(float(p) * alpha) + beta), 0, 255)))
+ *     with two separately rounded fp32 operations; the 8-bit BGR <-> HSV conversions are the ones docs/kernels/K14.md defines.
+ *   sem_seg (y, x): the label at source pixel (ny[Y], nx[X]), the source indices F.interpolate(mode = "nearest") applies along each axis to the
+ *     float64 labels (Detectron2 resizes a non-uint8 array with it, not with Pillow): ny int32 [new_h], nx int32 [new_w], built by the caller from
+ *     ATen itself (rba_amd.ops.nearest_index_tables; ATen's arithmetic there depends on the data type and the shape, docs/kernels/K14.md), values
+ *     outside the axis are brought back into it; an axis whose size does not change reads the index itself and its table may be NULL.
+ *   convert's two operations, and every fp32 product of the HSV -> BGR conversion, are rounded on their own: never a fused multiply-add.
+ *   image [3, pad_h, pad_w] pad value 128; sem_seg [pad_h, pad_w] pad value ignore_label; outlier_mask [ch, cw] (not padded) = ignore_label where
+ *     sem_seg == ignore_label, else 1 where sem_seg == ood_label, else 0; hist [256] = the count of each label value in the ch x cw crop (zeroed by
+ *     the call; integer atomics: bitwise reproducible).
+ * h, w, new_h, new_w, ch, cw >= 1; 0 <= y0, y0 + ch <= new_h, 0 <= x0, x0 + cw <= new_w; pad_h >= ch, pad_w >= cw; the box inside the source or
+ * absent; 0 <= ood_label <= 255; 3 h w and 3 pad_h pad_w < 2^31.  Anything else returns hipErrorInvalidValue without a launch; nothing is clamped. */
+typedef struct {
+  int enabled;                 /* 0: colour augmentation off, the other fields are ignored */
+  int brightness;
+  float beta;
+  int order;                   /* != 0: contrast, saturation, hue; 0: saturation, hue, contrast */
+  int contrast;
+  float contrast_alpha;
+  int saturation;
+  float saturation_alpha;
+  int hue;
+  int hue_delta;
+} rba_train_view_color;
+typedef struct {
+  const uint8_t* img;          /* [3,h,w] */
+  const uint8_t* lab;          /* [h,w] */
+  const uint8_t* lut;          /* 256 entries or NULL */
+  const uint8_t* obj;          /* [3,bh,bw] or NULL */
+  const uint8_t* objmask;      /* [bh,bw] or NULL */
+  const int32_t* kx;
+  const int32_t* bx;
+  const int32_t* ky;
+  const int32_t* by;
+  const int32_t* ny;           /* [new_h] or NULL */
+  const int32_t* nx;           /* [new_w] or NULL */
+  uint8_t* image;              /* [3,pad_h,pad_w] */
+  int64_t* sem_seg;            /* [pad_h,pad_w] */
+  int64_t* outlier_mask;       /* [ch,cw] */
+  int32_t* hist;               /* [256] */
+  int h, w, bh, bw, py, px, new_h, new_w, ksize_x, ksize_y, y0, x0, ch, cw, flip, pad_h, pad_w, ignore_label, ood_label;
+  rba_train_view_color color;
+} rba_train_view;
+int rba_train_view_u8(const rba_train_view* view /* host */, void* stream);
 
 #ifdef __cplusplus
 }

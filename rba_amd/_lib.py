@@ -63,6 +63,7 @@ SIGNATURES = {
     "rba_tta_merge_f32": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "rba_resize_u8_pil_bilinear": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
     "rba_confusion_accum": [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp],
+    "rba_train_view_u8": [_vp, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],
@@ -134,7 +135,24 @@ class TtaViews(ctypes.Structure):
                 ("flip", ctypes.c_int * TTA_MAX_VIEWS)]
 
 
-EXPECTED_ABI = 191        # rba_hip_version() the argtypes above were written for (include/rba_hip.h)
+class TrainViewColor(ctypes.Structure):
+    """rba_train_view_color of include/rba_hip.h"""
+    _fields_ = [("enabled", ctypes.c_int), ("brightness", ctypes.c_int), ("beta", ctypes.c_float), ("order", ctypes.c_int),
+                ("contrast", ctypes.c_int), ("contrast_alpha", ctypes.c_float), ("saturation", ctypes.c_int), ("saturation_alpha", ctypes.c_float),
+                ("hue", ctypes.c_int), ("hue_delta", ctypes.c_int)]
+
+
+TRAIN_VIEW_POINTERS = ("img", "lab", "lut", "obj", "objmask", "kx", "bx", "ky", "by", "ny", "nx", "image", "sem_seg", "outlier_mask", "hist")
+TRAIN_VIEW_INTS = ("h", "w", "bh", "bw", "py", "px", "new_h", "new_w", "ksize_x", "ksize_y", "y0", "x0", "ch", "cw", "flip", "pad_h", "pad_w",
+                   "ignore_label", "ood_label")
+
+
+class TrainView(ctypes.Structure):
+    """rba_train_view of include/rba_hip.h"""
+    _fields_ = ([(n, ctypes.c_void_p) for n in TRAIN_VIEW_POINTERS] + [(n, ctypes.c_int) for n in TRAIN_VIEW_INTS] + [("color", TrainViewColor)])
+
+
+EXPECTED_ABI = 191       # rba_hip_version() the argtypes above were written for (include/rba_hip.h)
 
 _lib = None
 

@@ -85,6 +85,14 @@ _DEFAULTS = {
                                  "OBJECT_MASK_THRESHOLD": 0.0, "OVERLAP_THRESHOLD": 0.0,
                                  "SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE": False}},
     },
+    # the keys rba_amd.dataset_mappers reads: detectron2/config/defaults.py INPUT, add_maskformer2_config (mask2former/config.py:13-20) and the
+    # reference's own (config.py:187-230); the Cityscapes base config sets MIN_SIZE_TRAIN 512 .. 2048, MAX_SIZE_TRAIN 4096, the absolute 512 x 1024
+    # crop, COLOR_AUG_SSD and FORMAT "RGB"
+    "INPUT": {"MIN_SIZE_TRAIN": [800], "MIN_SIZE_TRAIN_SAMPLING": "choice", "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,
+              "RANDOM_FLIP": "horizontal", "FORMAT": "BGR", "MASK_FORMAT": "polygon",
+              "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9], "SINGLE_CATEGORY_MAX_AREA": 1.0},
+              "DATASET_MAPPER_NAME": "mask_former_semantic", "COLOR_AUG_SSD": False, "SIZE_DIVISIBILITY": -1,
+              "OOD_LABEL": 254, "OOD_PROB": 0.2, "COCO_ROOT": "coco/", "COCO_PROXY_SIZE": 300, "REPEAT_INSTANCE_MASKS": 1},
     "SOLVER": {"FORCE_REGION_PARTITION": False},
     # detectron2/config/defaults.py TEST.AUG (rba_amd.test_time_augmentation); the Cityscapes base config sets [512 .. 1792], 4096, FLIP
     "TEST": {"AUG": {"ENABLED": False, "MIN_SIZES": [400, 500, 600, 700, 800, 900, 1000, 1100, 1200], "MAX_SIZE": 4000, "FLIP": True}},

@@ -148,6 +148,27 @@ class MaskFormer(nn.Module):
             mask_features, _, multi_scale_features = self.sem_seg_head.pixel_decoder.forward_features(features)
         return predictor(multi_scale_features, mask_features), sizes, padded
 
+    def prepare_targets(self, batched_inputs, padded):
+        """The criterion's targets from a training batch (maskformer_model.py:262-274, 358-379): per input, whose ``instances`` carry ``gt_classes`` and
+        ``gt_masks`` (rba_amd.dataset_mappers), {"labels": gt_classes, "masks": gt_masks zero-padded bottom / right to ``padded`` (H, W) -- the third
+        value of ``finetune_outputs`` --, and, where the input has them, "outlier_masks" and "sem_seg"}, on the model's device."""
+        h_pad, w_pad = int(padded[0]), int(padded[1])
+        dev = self.device
+        new_targets = []
+        for x in batched_inputs:
+            gt_masks = to_device(x["instances"].gt_masks, dev)
+            if gt_masks.shape[1] > h_pad or gt_masks.shape[2] > w_pad:
+                raise ValueError(f"prepare_targets: masks of size {tuple(gt_masks.shape[1:])} do not fit the padded size {(h_pad, w_pad)}")
+            padded_masks = torch.zeros((gt_masks.shape[0], h_pad, w_pad), dtype=gt_masks.dtype, device=dev)
+            padded_masks[:, : gt_masks.shape[1], : gt_masks.shape[2]] = gt_masks
+            entry = {"labels": to_device(x["instances"].gt_classes, dev), "masks": padded_masks}
+            if "outlier_mask" in x:
+                entry["outlier_masks"] = to_device(x["outlier_mask"], dev)
+            if "sem_seg" in x:
+                entry["sem_seg"] = to_device(x["sem_seg"], dev)
+            new_targets.append(entry)
+        return new_targets
+
     def _post(self, mask_cls, mask_pred, image_size, padded, want_sem_seg, want_argmax, score="rba"):
         """Up-sample (:294-299), semantic inference (:381-386), crop (:330-332), RbA (evaluate_ood.py:150)."""
         prob = _class_prob(mask_cls)

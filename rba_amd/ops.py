@@ -416,6 +416,101 @@ def confusion_accumulate(pred, gt, num_classes, conf, bad, ignore_label=255, lut
     _launch("rba_confusion_accum", _p(pred), _p(gt), gt.element_size(), pred.numel(), K, ignore, _p(lut), _p(conf), _p(bad))
 
 
+def nearest_index_tables(h, w, new_h, new_w):
+    """(ny int32 [new_h] | None, nx int32 [new_w] | None) on the CPU: the source row and column F.interpolate(size=(new_h, new_w), mode="nearest")
+    reads for every output row and column of a float64 [1,1,h,w] map -- what Detectron2's ResizeTransform gives the reference's float64 labels; None
+    for an axis whose size does not change (the index itself).  Asked of ATen itself, on a map of the very shape, once per shape: the CPU kernel's
+    index arithmetic depends on the data type (fp64 here; the fp32 rule of ATen's nearest_idx differs from it in two columns at 1024 -> 1228) and, at
+    small sizes, on the shape of the other axis too, so no closed form is restated (docs/kernels/K14.md).  The result is checked to be separable."""
+    h, w, new_h, new_w = int(h), int(w), int(new_h), int(new_w)
+    src = torch.arange(h * w, dtype=torch.float64).view(h, w)                        # the value names its pixel; exact below 2^53
+    out = torch.nn.functional.interpolate(src[None, None], size=(new_h, new_w), mode="nearest")[0, 0]
+    ny = torch.div(out[:, 0], w, rounding_mode="floor").to(torch.int64)
+    nx = (out[0, :] - ny[0] * w).to(torch.int64)
+    if int(ny.min()) < 0 or int(ny.max()) >= h or int(nx.min()) < 0 or int(nx.max()) >= w or not torch.equal(out, src[ny][:, nx]):
+        raise RbaHipError(f"F.interpolate(mode='nearest') of a {h} x {w} map to {new_h} x {new_w} is not a row table times a column table")
+    if (new_h == h and not torch.equal(ny, torch.arange(h))) or (new_w == w and not torch.equal(nx, torch.arange(w))):
+        raise RbaHipError(f"F.interpolate(mode='nearest') of a {h} x {w} map to {new_h} x {new_w} moves an axis whose size does not change")
+    return (None if new_h == h else ny.to(torch.int32)), (None if new_w == w else nx.to(torch.int32))
+
+
+_NEAREST_TABLES = {}      # (device index, h, w, new_h, new_w) -> (ny, nx) on the device
+
+
+def _nearest_tables(device, h, w, new_h, new_w):
+    key = (device.index, int(h), int(w), int(new_h), int(new_w))
+    t = _NEAREST_TABLES.get(key)
+    if t is None:
+        if len(_NEAREST_TABLES) >= 256:
+            _NEAREST_TABLES.clear()
+        t = _NEAREST_TABLES[key] = tuple(None if v is None else v.to(device) for v in nearest_index_tables(h, w, new_h, new_w))
+    return t
+
+
+@_hip_op
+def train_view(img, lab, params, obj=None, objmask=None, lut=None, ignore_label=255, ood_label=254, pad_size=None):
+    """K14.  img uint8 [3,h,w], lab uint8 [h,w] (through ``lut`` uint8 [256] when given), ``params`` a dataset_mappers.TrainViewParams (every sampled
+    decision: paste position, resize target, crop, colour legs, flip) and, where ``params.paste`` is set, the object ``obj`` uint8 [3,bh,bw] with its mask
+    ``objmask`` uint8 [bh,bw] -> (image uint8 [3,pad_h,pad_w], sem_seg int64 [pad_h,pad_w], outlier_mask int64 [ch,cw], hist int32 [256]): the training
+    view of MaskFormerSemanticCocoMixDatasetMapper in one launch, equal to the host composition in every element (docs/kernels/K14.md).  ``pad_size``
+    (pad_h, pad_w): the output canvas, the crop's size when None.  Nothing is read back.  The shape contract (crop inside the resized frame, box inside
+    the source, canvas no smaller than the crop) is the entry point's: a violation raises RbaHipError, nothing is clamped."""
+    _chk(img, "img", dtype=torch.uint8, dim=3)
+    _chk(lab, "lab", dtype=torch.uint8, dim=2)
+    h, w = int(img.shape[1]), int(img.shape[2])
+    if img.shape[0] != 3 or tuple(lab.shape) != (h, w):
+        raise RbaHipError(f"train_view needs img [3,h,w] and lab [h,w], got {tuple(img.shape)} and {tuple(lab.shape)}")
+    v = _lib.TrainView()
+    v.img, v.lab, v.h, v.w = img.data_ptr(), lab.data_ptr(), h, w
+    if lut is not None:
+        _chk(lut, "lut", dtype=torch.uint8, dim=1)
+        if lut.numel() != 256:
+            raise RbaHipError(f"lut must have 256 entries, got {lut.numel()}")
+        v.lut = lut.data_ptr()
+    if params.paste is not None:
+        _chk(obj, "obj", dtype=torch.uint8, dim=3)
+        _chk(objmask, "objmask", dtype=torch.uint8, dim=2)
+        if obj.shape[0] != 3 or tuple(obj.shape[1:]) != tuple(objmask.shape) or objmask.numel() < 1:
+            raise RbaHipError(f"train_view needs obj [3,bh,bw] and objmask [bh,bw], got {tuple(obj.shape)} and {tuple(objmask.shape)}")
+        v.obj, v.objmask, v.bh, v.bw = obj.data_ptr(), objmask.data_ptr(), int(objmask.shape[0]), int(objmask.shape[1])
+        v.py, v.px = int(params.paste[0]), int(params.paste[1])
+    dev = img.device
+    v.new_h, v.new_w = int(params.new_h), int(params.new_w)
+    if min(v.new_h, v.new_w) < 1:
+        raise RbaHipError(f"train_view: empty resize target {(v.new_h, v.new_w)}")
+    tables = []                                                  # kept alive until the launch is enqueued
+    if v.new_w != w:
+        kx, bx, v.ksize_x = _pil_tables(dev, w, v.new_w)
+        v.kx, v.bx = kx.data_ptr(), bx.data_ptr()
+        tables += [kx, bx]
+    if v.new_h != h:
+        ky, by, v.ksize_y = _pil_tables(dev, h, v.new_h)
+        v.ky, v.by = ky.data_ptr(), by.data_ptr()
+        tables += [ky, by]
+    if v.new_w != w or v.new_h != h:
+        ny, nx = _nearest_tables(dev, h, w, v.new_h, v.new_w)
+        v.ny, v.nx = _p(ny), _p(nx)
+        tables += [ny, nx]
+    v.y0, v.x0, v.ch, v.cw = (int(c) for c in params.crop)
+    v.pad_h, v.pad_w = (v.ch, v.cw) if pad_size is None else (int(pad_size[0]), int(pad_size[1]))
+    v.flip, v.ignore_label, v.ood_label = int(bool(params.flip)), int(ignore_label), int(ood_label)
+    if min(v.ch, v.cw) < 1 or v.pad_h < v.ch or v.pad_w < v.cw:
+        raise RbaHipError(f"train_view: crop {(v.ch, v.cw)} and canvas {(v.pad_h, v.pad_w)}: the crop is non-empty and the canvas no smaller")
+    c = params.color
+    if c is not None:
+        k = v.color
+        k.enabled, k.brightness, k.beta, k.order = 1, int(bool(c.brightness)), float(c.beta), int(bool(c.order))
+        k.contrast, k.contrast_alpha, k.saturation, k.saturation_alpha = int(bool(c.contrast)), float(c.contrast_alpha), int(bool(c.saturation)), float(c.saturation_alpha)
+        k.hue, k.hue_delta = int(bool(c.hue)), int(c.hue_delta)
+    image = torch.empty((3, v.pad_h, v.pad_w), dtype=torch.uint8, device=dev)
+    sem_seg = torch.empty((v.pad_h, v.pad_w), dtype=torch.int64, device=dev)
+    outlier_mask = torch.empty((v.ch, v.cw), dtype=torch.int64, device=dev)
+    hist = torch.empty(256, dtype=torch.int32, device=dev)
+    v.image, v.sem_seg, v.outlier_mask, v.hist = image.data_ptr(), sem_seg.data_ptr(), outlier_mask.data_ptr(), hist.data_ptr()
+    _launch("rba_train_view_u8", ctypes.addressof(v))
+    return image, sem_seg, outlier_mask, hist
+
+
 # K13's launch rule (csrc/confusion.hip), for tests that size a map to a number of sweeps of the capped grid
 CONFUSION_THREADS, CONFUSION_TILE, CONFUSION_GRID_CAP, CONFUSION_LDS_MAX_K = 256, 16, 512, 126
 
