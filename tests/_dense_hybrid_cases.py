@@ -1,11 +1,13 @@
 """Shared by tests/test_dense_hybrid_loss_gpu.py, tests/test_densehybrid_finetune_gpu.py and tools/dense_hybrid_loss_probe.py: the torch
 restatement of the reference's DenseHybrid loss, seeded inputs and the fp64 / fp32 CPU autograd truths.
 
-The restatement (``ref_tail``, ``ref_densehybrid_loss``) is written from mask2former/modeling/criterion.py:93-97 and :390-433 of the reference;
-that file cannot be imported without Detectron2, so -- like tests/_rba_bwd_cases.py -- its parity is UNPINNED BY REFERENCE CODE.  Two departures,
-both of the kernel's contract: the targets are not written (the reference relabels them in place), and a label that is neither a class nor 254
-is ignored by the segmentation term whatever its value (the reference maps 254 and 255 to ``ignore_index``; any other value is an index error
-there).  Error metric, bar and checks are those of tests/_rba_bwd_cases.py and tests/_point_loss_cases.py.
+The restatement (``ref_tail``, ``ref_densehybrid_loss``) is written from mask2former/modeling/criterion.py:93-97 and :390-433 of the reference.
+Its parity is PINNED BY REFERENCE CODE inside the reference's domain (labels that are a class, 254 or 255): tests/golden/g9_criterion.npz holds what
+the reference's own ``densehybrid_loss`` computes (loss and float64 gradients at "small", at K = 19 and at the "crop"), and
+tests/test_criterion_reference_cpu.py holds this restatement to it at relative 1e-12.  One departure, of the kernel's contract and outside that
+domain (so against this restatement only): a label that is neither a class nor 254 is ignored by the segmentation term whatever its value (the
+reference maps 254 and 255 to ``ignore_index``; any other value is an index error there).  The targets are not written, here or in the reference:
+its relabelling acts on a ``torch.cat`` copy.  Error metric, bar and checks are those of tests/_rba_bwd_cases.py and tests/_point_loss_cases.py.
 """
 import functools
 

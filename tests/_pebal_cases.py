@@ -2,12 +2,15 @@
 and tools/pebal_loss_probe.py: the torch restatements of the reference's gambler, smoothness and sparsity losses, seeded inputs and the fp64 /
 fp32 CPU autograd truths.
 
-The restatements are written from mask2former/modeling/criterion.py:245-388 of the reference; that file cannot be imported without Detectron2
-and torchvision is absent, so -- like tests/_rba_bwd_cases.py and tests/_dense_hybrid_cases.py -- their parity is UNPINNED BY REFERENCE CODE.
-``ref_blur`` is torchvision's ``GaussianBlur(7, sigma=1)`` restated: the 1-D kernel exp(-0.5 (x / sigma)^2) on linspace(-(k-1)/2, (k-1)/2, k)
-normalised to 1, the 2-D kernel their outer product, reflect padding, a per-plane correlation.  Two departures, both of the kernel's contract:
-the targets are not written (the reference relabels both in place), and an inlier pixel whose ``sem_seg`` value is not a class is void (an
-index error in the reference).  ``self.pebal_reward`` of the reference is dead code (``reward.nelement() > 0`` always holds) and is not
+The restatements are written from mask2former/modeling/criterion.py:245-388 of the reference.  Their parity is PINNED BY REFERENCE CODE inside the
+reference's domain: tests/golden/g9_criterion.npz holds what the reference's own ``gambler_loss`` (both branches, K = 19 -- it hard-codes 19
+channels), ``smoothness_loss`` and ``sparsity_loss`` compute, losses and float64 gradients, and tests/test_criterion_reference_cpu.py holds these
+restatements and ``ref_pebal_entry`` (through the recipe's ``SetCriterion.forward``) to it at relative 1e-12.  What stays restated and unpinned:
+``ref_blur``, torchvision's ``GaussianBlur(7, sigma=1)`` (torchvision is absent; the generator's stand-in is the same definition): the 1-D kernel
+exp(-0.5 (x / sigma)^2) on linspace(-(k-1)/2, (k-1)/2, k) normalised to 1, the 2-D kernel their outer product, reflect padding, a per-plane
+correlation.  One departure, of the kernel's contract and outside the reference's domain (so against these restatements only): an inlier pixel
+whose ``sem_seg`` value is not a class is void (an index error in the reference).  The targets are not written, here or in the reference: its
+``labels[...] = 0`` lines act on a ``torch.cat`` copy.  ``self.pebal_reward`` of the reference is dead code (``reward.nelement() > 0`` always holds) and is not
 restated.  Error metric, bar and checks are those of tests/_rba_bwd_cases.py and tests/_point_loss_cases.py.
 """
 import functools

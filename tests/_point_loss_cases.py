@@ -3,6 +3,13 @@ restatement of what K8 computes -- detectron2's point_sample, the two losses of 
 matcher's cost in its ORIGINAL pos / neg form (matcher.py:15-62, 105-149; the kernel uses softplus(x) - x t) and the uncertainty selection
 (criterion.py:76-90 + detectron2's get_uncertain_point_coords_with_randomness).  Everything is dtype-generic: the same function in double is the
 truth and in float is b, the fp32-CPU error of the same case.  Error metric, bar and check are those of tests/_rba_bwd_cases.py.
+
+Parity: ``ref_mask_losses``, ``ref_match_cost``, ``ref_loss_labels`` and ``ref_criterion`` are PINNED BY REFERENCE CODE -- tests/golden/g9_criterion.npz
+holds what the reference's own ``loss_masks``, ``loss_labels``, ``dice_loss``, ``sigmoid_ce_loss``, ``batch_dice_loss``, ``batch_sigmoid_ce_loss``,
+``HungarianMatcher`` (cost matrix and assignment) and ``SetCriterion.forward`` compute, and tests/test_criterion_reference_cpu.py holds these
+restatements to it at relative 1e-12 (2^-23 where the reference computes in float32).  ``ref_point_sample`` is held there against the generator's
+stand-in for Detectron2's ``point_sample`` (``grid_sample(input, 2 coords - 1)``, restated: unpinned), and ``ref_select`` -- the uncertainty
+importance sampling -- remains unpinned: the fixture hands the reference's loss its stored coordinates.
 """
 import functools
 

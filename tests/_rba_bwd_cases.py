@@ -1,9 +1,12 @@
 """Shared by tests/test_rba_backward_cpu.py and tests/test_rba_backward_gpu.py: the torch restatement of the reference's outlier loss, the
 case table of K1's backward, the error metric and its bar.
 
-The restatement below (``ref_score``, ``ref_outlier_loss``) is written from mask2former/modeling/criterion.py:443-503 of the reference; that
-file cannot be imported without Detectron2, so -- like the other such cases of DESIGN.md section 2 -- its parity is UNPINNED BY REFERENCE CODE:
-it is checked against the mathematics (torch.autograd.gradcheck in double, test_rba_backward_cpu.py), and it is the truth the GPU tests use.
+The restatement below (``ref_score``, ``ref_outlier_loss``) is written from mask2former/modeling/criterion.py:443-518 of the reference.  Its parity
+is PINNED BY REFERENCE CODE: tests/golden/g9_criterion.npz holds what the reference's own ``SetCriterion.outlier_loss`` computes (loss and float64
+gradients, three targets x four functions, with and without outlier pixels, at the "small" and "crop" shapes below), and
+tests/test_criterion_reference_cpu.py holds this restatement to it at relative 1e-12 (2^-23 for ``binary_cross_entropy``, whose target the reference
+casts to float32).  It is also checked against the mathematics (torch.autograd.gradcheck in double, test_rba_backward_cpu.py), and it is the truth
+the GPU tests use.
 """
 import functools
 

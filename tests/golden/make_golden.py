@@ -19,6 +19,16 @@ detectron2.structures / cv2), are restated here; DESIGN.md lists them as "parity
 unpinned by the reference's own code".  Everything else in a fixture is produced by the
 reference's code itself.
 
+``--only g9_criterion`` writes g9_criterion.npz from the reference's ``modeling/criterion.py``
+and ``modeling/matcher.py`` (losses, float64 gradients, the matcher's cost matrix and
+assignment, ``SetCriterion.forward`` of the three fine-tune recipes).  Its further stand-ins
+are listed in ``_criterion_modules``; of those, ``point_sample`` (Detectron2 v0.6's
+``grid_sample(input, 2 coords - 1)``) and ``transforms.GaussianBlur(7, sigma=1)``
+(torchvision's published definition) carry arithmetic and stay unpinned, and the importance
+sampling of ``get_uncertain_point_coords_with_randomness`` is not restated at all: the
+stand-in returns the fixture's stored coordinates.  ``--only g9_criterion --check``
+regenerates the arrays in memory and compares them with the committed file.
+
     python tests/golden/make_golden.py [--only NAME] [--full]
 
 ``--full`` additionally generates the two full-size (Swin-B) sampled fixtures (about
@@ -565,10 +575,347 @@ def g_metrics(R):
     save("g6_metrics", **out)
 
 
+# --------------------------------------------------------------------------------------
+# G9: the reference's criterion.py and matcher.py
+# --------------------------------------------------------------------------------------
+def _criterion_modules():
+    """Imports mask2former/modeling/criterion.py and matcher.py behind stand-ins (``_install_import_stubs`` must have run).  The stand-ins are
+    this repository's code; these carry arithmetic and stay UNPINNED by reference code:
+
+    * ``point_sample``: Detectron2 v0.6's definition (projects/PointRend/point_rend/point_features.py), ``grid_sample(input, 2 coords - 1)``
+      with the 3-D coordinate convenience -- restated, as ``Conv2d`` / ``get_norm`` above are.
+    * ``transforms.GaussianBlur(7, sigma=1)``: torchvision's published definition (``tests/_pebal_cases.ref_blur`` is the same restatement,
+      cross-checked against SciPy in tests/test_oracle_golden.py) -- unpinned for this one function.
+
+    These carry none: ``get_uncertain_point_coords_with_randomness`` returns the point coordinates the fixture holds (the importance sampling
+    itself is NOT restated here and remains unpinned: tests/test_point_loss_*.py check the product's against Detectron2's definition as read);
+    ``get_world_size() -> 1``; ``torchvision._is_tracing() -> False`` (read by the reference's own ``nested_tensor_from_tensor_list``);
+    ``is_dist_avail_and_initialized()`` is the reference's own and returns False in a single process.  The matcher draws its points with ``torch.rand`` and hands its cost matrix only to
+    ``linear_sum_assignment``: the imported matcher module gets a ``torch`` proxy whose ``rand`` returns the fixture's coordinates and a
+    recording wrapper around SciPy's ``linear_sum_assignment``.  No reference code is edited or copied.
+
+    -> namespace(crit, matcher, state); state.loss_coords / state.matcher_coords are what the stand-ins return (the matcher's in state.dtype, the
+    type of the run), state.costs collects every C."""
+    from scipy.optimize import linear_sum_assignment
+
+    state = types.SimpleNamespace(loss_coords=None, matcher_coords=None, costs=[], dtype=torch.float32)
+
+    def mod(name, **attrs):
+        m = types.ModuleType(name)
+        m.__dict__.update(attrs)
+        sys.modules[name] = m
+        return m
+
+    def point_sample(input, point_coords, **kwargs):
+        add_dim = point_coords.dim() == 3
+        if add_dim:
+            point_coords = point_coords.unsqueeze(2)
+        output = F.grid_sample(input, 2.0 * point_coords - 1.0, **kwargs)
+        return output.squeeze(3) if add_dim else output
+
+    def get_uncertain_point_coords_with_randomness(coarse_logits, uncertainty_func, num_points, oversample_ratio, importance_sample_ratio):
+        assert state.loss_coords.shape[0] == coarse_logits.shape[0], "fixture: one row of loss coordinates per matched mask"
+        return state.loss_coords.to(coarse_logits)
+
+    class GaussianBlur:
+        def __init__(self, kernel_size, sigma):
+            self.kernel_size, self.sigma = int(kernel_size), float(sigma)
+
+        def __call__(self, img):                                      # [..., C, H, W]; one kernel, reflect padding, a per-channel correlation
+            half = (self.kernel_size - 1) * 0.5
+            x = torch.linspace(-half, half, steps=self.kernel_size, dtype=img.dtype, device=img.device)
+            pdf = torch.exp(-0.5 * (x / self.sigma).pow(2))
+            k1 = pdf / pdf.sum()
+            k2 = torch.mm(k1[:, None], k1[None, :])
+            r = self.kernel_size // 2
+            c = img.shape[-3]
+            flat = F.pad(img.reshape(-1, c, *img.shape[-2:]), (r, r, r, r), mode="reflect")
+            return F.conv2d(flat, k2.expand(c, 1, -1, -1), groups=c).reshape(img.shape)
+
+    mod("detectron2.utils.comm", get_world_size=lambda: 1)
+    mod("detectron2.projects")
+    mod("detectron2.projects.point_rend")
+    mod("detectron2.projects.point_rend.point_features", point_sample=point_sample,
+        get_uncertain_point_coords_with_randomness=get_uncertain_point_coords_with_randomness)
+    tv = mod("torchvision", _is_tracing=lambda: False)
+    tv.transforms = mod("torchvision.transforms", GaussianBlur=GaussianBlur)
+    ns = types.ModuleType("mask2former.utils")
+    ns.__path__ = [os.path.join(REF, "mask2former", "utils")]
+    sys.modules["mask2former.utils"] = ns
+    crit = importlib.import_module("mask2former.modeling.criterion")
+    matcher = importlib.import_module("mask2former.modeling.matcher")
+
+    class TorchWithFixedRand:
+        def __getattr__(self, name):
+            return getattr(torch, name)
+
+        def rand(self, *size, **kw):
+            assert tuple(size) == (1,) + tuple(state.matcher_coords.shape), "fixture: the matcher's draw has the stored coordinates' shape"
+            return state.matcher_coords[None].to(state.dtype)
+
+    def recording_lsa(C):
+        state.costs.append(C.clone())
+        return linear_sum_assignment(C)
+
+    matcher.torch = TorchWithFixedRand()
+    matcher.linear_sum_assignment = recording_lsa
+    return types.SimpleNamespace(crit=crit, matcher=matcher, state=state)
+
+
+def build_g9(R):
+    """G9: ``SetCriterion``'s losses, the module-level loss functions, ``HungarianMatcher`` and ``SetCriterion.forward`` of the reference, on the
+    CPU in float64 and float32 -> the arrays of g9_criterion.npz (layout: tests/_criterion_ref_cases.py)."""
+    from tests import _criterion_ref_cases as G
+    from tests import _dense_hybrid_cases as DH
+    from tests import _pebal_cases as PB
+    from tests import _rba_bwd_cases as RB
+    M = _criterion_modules()
+    st = M.state
+    out = {}
+
+    def criterion(K, losses=(), weights=None, matcher=None, **settings):
+        kw = dict(smoothness_score="none", score_norm="none", outlier_loss_target="none", outlier_loss_func="squared_hinge")
+        kw.update(settings)
+        return M.crit.SetCriterion(K, matcher, weights or {}, G.EOS, list(losses), 0, 3.0, 0.75, inlier_upper_threshold=G.THR_IN,
+                                   outlier_lower_threshold=G.THR_OUT, pebal_reward=4.5, ood_reg=G.OOD_REG, densehybrid_beta=G.BETA, **kw)
+
+    def pin(key, fn, leaves, sums=False, store=True):
+        """fn(**leaves in one dtype) -> scalar.  float64 and float32 runs of the reference; inputs stored as float32 (or their crc32)"""
+        res = {}
+        for dtype in (torch.float64, torch.float32):
+            lv = {k: v.to(dtype).clone().requires_grad_(True) for k, v in leaves.items()}
+            st.dtype = dtype
+            torch.set_default_dtype(dtype)                            # the thresholds' ``torch.tensor(float)`` of the mse / l1 branches follow the run's type
+            try:
+                loss = fn(**lv)
+            finally:
+                torch.set_default_dtype(torch.float32)
+                st.dtype = torch.float32
+            if loss.requires_grad and bool(torch.isfinite(loss)):
+                loss.backward()
+            res[dtype] = (loss.detach(), {k: (torch.zeros_like(v) if v.grad is None else v.grad) for k, v in lv.items()})
+        (l64, g64), (l32, g32) = res[torch.float64], res[torch.float32]
+        out[key + "/l64"], out[key + "/l32"] = np.float64(l64.double().item()), np.float64(l32.double().item())
+        out[key + "/l64_is_f32"] = np.bool_(l64.dtype == torch.float32)   # loss_labels' ``.float()``, the BCE's ``ood_mask.float()`` target
+        for k in leaves:
+            if sums:
+                out[f"{key}/crc_{k}"] = G.crc(leaves[k])
+                for ax, s in G.grad_sums(g64[k]).items():
+                    out[f"{key}/s_{k}_{ax}"] = np_(s)
+            else:
+                if store:
+                    out[f"{key}/in_{k}"] = np_(leaves[k])
+                out[f"{key}/g_{k}"] = np_(g64[k].double())
+            out[f"{key}/b_{k}"] = np.float64(RB.err(g32[k], g64[k].double()) if float(g64[k].abs().max()) > 0 else 0.0)
+        return l64
+
+    def store_targets(key, targets, sums=False):
+        for i, tg in enumerate(targets):
+            for k, v in tg.items():
+                if sums:
+                    out[f"{key}/crc_t{i}_{k}"] = G.crc(v)
+                elif k == "masks":
+                    out[f"{key}/t{i}_masks_bits"] = np.packbits(np_(v).astype(np.uint8).reshape(-1))
+                    out[f"{key}/t{i}_masks_shape"] = np.array(v.shape, dtype=np.int64)
+                else:
+                    out[f"{key}/t{i}_{k}"] = np_(v).astype(np.uint8 if k in ("outlier_masks", "sem_seg") else np.int64)
+
+    def cloned(targets, dtype):
+        return [{k: (v.to(dtype) if v.is_floating_point() else v.clone()) for k, v in tg.items()} for tg in targets]
+
+    def dense(method, targets):
+        return lambda **lv: list(method(lv, cloned(targets, lv["pred_masks"].dtype), None, None).values())[0]
+
+    # ---- "small": the outlier loss, 3 (target, score_norm) x 4 functions x with / without outlier pixels
+    B, Q, K, h, w, H, W = G.SMALL
+    for combo in RB.COMBOS:
+        for outliers in (True, False):
+            lg, mk, lab = RB.loss_inputs("small", combo, outliers)
+            ikey = f"small/outlier/{'_'.join(combo)}/{'out' if outliers else 'noout'}"
+            out[ikey + "/in_pred_logits"], out[ikey + "/in_pred_masks"] = np_(lg), np_(mk)
+            store_targets(ikey, [{"outlier_masks": x} for x in lab])
+            for func in RB.FUNCS:
+                c = criterion(K, outlier_loss_target=combo[0], score_norm=combo[1], outlier_loss_func=func)
+                pin(f"{ikey}/{func}", dense(c.outlier_loss, [{"outlier_masks": x} for x in lab]), {"pred_logits": lg, "pred_masks": mk}, store=False)
+    # ---- "small": smoothness and sparsity, both scores, with and without outlier_masks in the targets
+    lg, mk, om, ss = PB.loss_inputs("small")
+    om, ss = G.domain_pebal(om, ss, K)
+    out["small/reg/in_pred_logits"], out["small/reg/in_pred_masks"] = np_(lg), np_(mk)
+    store_targets("small/reg", [{"outlier_masks": x} for x in om])
+    for score in ("nls", "energy"):
+        c = criterion(K, smoothness_score=score)
+        leaves = {"pred_logits": lg, "pred_masks": mk}
+        pin(f"small/reg/{score}/smoothness", dense(c.smoothness_loss, [{"outlier_masks": x} for x in om]), leaves, store=False)
+        pin(f"small/reg/{score}/sparsity", dense(c.sparsity_loss, [{"outlier_masks": x} for x in om]), leaves, store=False)
+        pin(f"small/reg/{score}/sparsity_unlabelled", dense(c.sparsity_loss, [{} for _ in om]), leaves, store=False)
+    # ---- "small" and "k19": DenseHybrid; without a 254 pixel the reference divides by the numel() of an empty selection
+    for case, shape, seed in (("small", G.SMALL, None), ("k19", G.K19, 12200)):
+        if seed is None:
+            lg, mk, ood, lab = DH.loss_inputs("small")
+            lab = G.domain_sem_seg(lab, shape[2])
+        else:
+            lg, mk, ood, lab = G.dense_inputs(shape, seed)
+        c = criterion(shape[2])
+        leaves = {"pred_logits": lg, "pred_masks": mk, "ood_pred": ood}
+        store_targets(f"{case}/densehybrid", [{"sem_seg": x} for x in lab])
+        l64 = pin(f"{case}/densehybrid", dense(c.densehybrid_loss, [{"sem_seg": x, "outlier_masks": x} for x in lab]), leaves)
+        assert bool(torch.isfinite(l64))
+        if case == "small":
+            none = torch.where(lab == DH.OUTLIER, torch.full_like(lab, 255), lab)
+            with torch.no_grad():
+                bad = dense(c.densehybrid_loss, [{"sem_seg": x, "outlier_masks": x} for x in none])(**{k: v.double() for k, v in leaves.items()})
+            assert not bool(torch.isfinite(bad)), "the reference's densehybrid_loss without an outlier pixel was expected not to be finite"
+            out["small/densehybrid/no_outlier_pixel_finite"] = np.bool_(torch.isfinite(bad))
+    # ---- "k19": the gambler loss in both branches (the reference hard-codes 19 channels)
+    B, Q, K, h, w, H, W = G.K19
+    lg, mk, _, lab = G.dense_inputs(G.K19, 12200)
+    om, ss = G.planes_of(lab)
+    for branch, o in (("out", om), ("noout", G.without_outliers(om))):
+        tg = [{"outlier_masks": a, "sem_seg": b} for a, b in zip(o, ss)]
+        r64 = PB.ref_gambler_tail(PB.ref_sem_full(lg.double(), mk.double()), PB.gambler_labels(o, ss, K))[1]["R"]
+        assert float(r64.min()) >= PB.MIN_R, f"fixture k19: min R64 = {float(r64.min()):.3g} < {PB.MIN_R}"
+        assert bool((o == 1).any()) == (branch == "out") and bool((o == 0).any())
+        store_targets(f"k19/gambler/{branch}", tg)
+        pin(f"k19/gambler/{branch}", dense(criterion(K).gambler_loss, tg), {"pred_logits": lg, "pred_masks": mk}, store=(branch == "out"))
+    # ---- "small": loss_labels and loss_masks (ragged target counts, two target sizes, one image without a target)
+    K = G.SMALL[2]
+    lg, mk, targets, indices, coords = G.set_inputs()
+    c = criterion(K)
+    store_targets("small/set", targets)
+    out["small/set/coords"] = np_(coords)
+    for b, (i, j) in enumerate(indices):
+        out[f"small/set/idx{b}_i"], out[f"small/set/idx{b}_j"] = np_(i), np_(j)
+    pin("small/set/loss_ce", lambda pred_logits: c.loss_labels({"pred_logits": pred_logits}, targets, indices, G.SET_NUM_MASKS)["loss_ce"], {"pred_logits": lg})
+    st.loss_coords = coords
+    for name in ("loss_mask", "loss_dice"):
+        pin(f"small/set/{name}", lambda pred_masks: c.loss_masks({"pred_masks": pred_masks}, cloned(targets, pred_masks.dtype), indices, G.SET_NUM_MASKS)[name],
+            {"pred_masks": mk}, store=(name == "loss_mask"))
+    # ---- the module-level functions on plain [N,P] / [Q,P] x [T,P] arrays
+    gen = torch.Generator().manual_seed(12150)
+    x, y = 3.0 * torch.randn(5, 37, generator=gen), torch.rand(5, 37, generator=gen)
+    xq, yt = 3.0 * torch.randn(9, 37, generator=gen), torch.rand(4, 37, generator=gen)
+    out.update({"small/fn/x": np_(x), "small/fn/y": np_(y), "small/fn/xq": np_(xq), "small/fn/yt": np_(yt), "small/fn/num_masks": np.float64(3.0)})
+    for dt, tag in ((torch.float64, "64"),):
+        out["small/fn/dice_loss" + tag] = np_(M.crit.dice_loss(x.to(dt), y.to(dt), 3.0).double())
+        out["small/fn/sigmoid_ce_loss" + tag] = np_(M.crit.sigmoid_ce_loss(x.to(dt), y.to(dt), 3.0).double())
+        out["small/fn/batch_dice_loss" + tag] = np_(M.matcher.batch_dice_loss(xq.to(dt), yt.to(dt)).double())
+        out["small/fn/batch_sigmoid_ce_loss" + tag] = np_(M.matcher.batch_sigmoid_ce_loss(xq.to(dt), yt.to(dt)).double())
+
+    # ---- the matcher: the captured float32 C, the assignment, and a float64 evaluation of the same cost by the reference's own functions
+    def cost64(logits, pred, target, pts):
+        from detectron2.projects.point_rend.point_features import point_sample
+        pts = pts.double()[None]
+        xs = point_sample(pred.double()[:, None], pts.repeat(pred.shape[0], 1, 1), align_corners=False).squeeze(1)
+        ts = point_sample(target["masks"].double()[:, None], pts.repeat(target["masks"].shape[0], 1, 1), align_corners=False).squeeze(1)
+        return (G.MATCHER_WEIGHTS["cost_mask"] * M.matcher.batch_sigmoid_ce_loss(xs, ts) + G.MATCHER_WEIGHTS["cost_class"] * -logits.double().softmax(-1)[:, target["labels"]]
+                + G.MATCHER_WEIGHTS["cost_dice"] * M.matcher.batch_dice_loss(xs, ts))
+
+    def assert_stable(c32, c64, idx, what):
+        from scipy.optimize import linear_sum_assignment
+        i64, j64 = linear_sum_assignment(c64.numpy())
+        assert np.array_equal(i64, np_(idx[0])) and np.array_equal(j64, np_(idx[1])), f"fixture {what}: the float64 cost gives another assignment"
+        assert c32.dtype == torch.float32
+
+    ref_matcher = M.matcher.HungarianMatcher(num_points=0, **G.MATCHER_WEIGHTS)
+    for n, shape in enumerate(G.MATCHER_SHAPES):
+        logits, pred, target, pts, centres = G.matcher_inputs(shape, 12400 + n)
+        key = f"matcher/{n}"
+        st.matcher_coords, st.costs = centres, []                     # the float32 comparison's points: sampling is exact there
+        ref_matcher.num_points = shape[2]
+        ref_matcher({"pred_logits": logits, "pred_masks": pred}, [{"labels": target["labels"], "masks": target["masks"]}])
+        out.update({key + "/centres": np_(centres), key + "/C32_centres": np_(st.costs[0])})
+        st.matcher_coords, st.costs = pts, []
+        ref_matcher.num_points = shape[2]
+        idx = ref_matcher({"pred_logits": logits, "pred_masks": pred}, [{"labels": target["labels"], "masks": target["masks"]}])
+        c64 = cost64(logits[0], pred[0], target, pts)
+        assert_stable(st.costs[0], c64, idx[0], key)
+        out.update({key + "/in_pred_logits": np_(logits), key + "/in_pred_masks": np_(pred), key + "/coords": np_(pts), key + "/C32": np_(st.costs[0]),
+                    key + "/C64": np_(c64), key + "/idx_i": np_(idx[0][0]), key + "/idx_j": np_(idx[0][1]), key + "/b": np.float64(RB.err(st.costs[0], c64))})
+        store_targets(key, [{"labels": target["labels"], "masks": target["masks"]}])
+    # an image without a target: what the reference does is recorded, nothing else
+    logits, pred, target, pts, _ = G.matcher_inputs(G.MATCHER_SHAPES[0], 12400)
+    st.matcher_coords, st.costs = pts, []
+    ref_matcher.num_points = G.MATCHER_SHAPES[0][2]
+    try:
+        idx = ref_matcher({"pred_logits": logits, "pred_masks": pred}, [{"labels": target["labels"][:0], "masks": target["masks"][:0]}])
+        out["matcher/empty/raises"], out["matcher/empty/idx_len"] = np.bool_(False), np.int64(len(idx[0][0]))
+    except (RuntimeError, ValueError) as e:
+        print(f"  matcher, T = 0: the reference raises {type(e).__name__}: {str(e).splitlines()[0]}")
+        out["matcher/empty/raises"] = np.bool_(True)
+
+    # ---- SetCriterion.forward of the three recipes' loss lists
+    B, Q, K, h, w, H, W = G.K19
+    leaves_all, targets, mpts, lpts = G.forward_inputs()
+    store_targets("forward", targets)
+    out["forward/matcher_coords"], out["forward/loss_coords"] = np_(mpts), np_(lpts)
+    for k, v in leaves_all.items():
+        out["forward/in_" + k] = np_(v)
+    st.matcher_coords, st.loss_coords = mpts, lpts
+    ref_matcher.num_points = G.FWD_PM
+    for name, spec in G.FORWARDS.items():
+        c = criterion(K, spec["losses"], spec["weights"], ref_matcher, **spec["settings"])
+        names = G.forward_leaves(name)
+        seen = {}
+
+        def total(**lv):
+            st.costs = []
+            losses = c(G.outputs_of({**{k: v.to(lv["pred_masks"].dtype) for k, v in leaves_all.items()}, **lv}, ood=(name == "densehybrid")),
+                       cloned(targets, lv["pred_masks"].dtype))
+            seen[lv["pred_masks"].dtype] = ({k: v.detach() for k, v in losses.items()}, [x.clone() for x in st.costs])
+            return sum(v * G.weight_of(name, k) for k, v in losses.items())
+
+        pin(f"forward/{name}/total", total, {k: leaves_all[k] for k in names}, store=False)
+        (l64, c64s), (l32, c32s) = seen[torch.float64], seen[torch.float32]
+        assert sorted(l64) == sorted(l32) and all(RB.err(a, b.double()) < 1e-5 for a, b in zip(c32s, c64s))
+        out[f"forward/{name}/keys"] = np.array(sorted(l64))
+        for k in l64:
+            out[f"forward/{name}/{k}/l64"], out[f"forward/{name}/{k}/l32"] = np.float64(l64[k].double().item()), np.float64(l32[k].double().item())
+        if name == "mix":                                             # the assignment of every entry and image, once
+            entries = [{k: leaves_all[k] for k in ("pred_logits", "pred_masks")}] + G.outputs_of(leaves_all)["aux_outputs"]
+            for e, entry in enumerate(entries):
+                st.costs = []
+                idx = ref_matcher(entry, targets)
+                for b_ in range(B):
+                    assert_stable(st.costs[b_], cost64(entry["pred_logits"][b_], entry["pred_masks"][b_], targets[b_], mpts), idx[b_], f"forward entry {e} image {b_}")
+                    out[f"forward/idx{e}_{b_}_i"], out[f"forward/idx{e}_{b_}_j"] = np_(idx[b_][0]), np_(idx[b_][1])
+
+    # ---- "crop": scalars, sums and checksums only
+    K = G.CROP[2]
+    for case, (leaves, tg) in G.crop_cases().items():
+        store_targets("crop/" + case, tg, sums=True)
+        if case.startswith("outlier/"):
+            combo = tuple(case.split("/")[1].split("_"))
+            for func in RB.FUNCS:
+                c = criterion(K, outlier_loss_target=combo[0], score_norm=combo[1], outlier_loss_func=func)
+                pin(f"crop/{case}/{func}", dense(c.outlier_loss, tg), leaves, sums=True)
+        elif case == "densehybrid":
+            pin("crop/densehybrid/loss", dense(criterion(K).densehybrid_loss, tg), leaves, sums=True)
+        else:
+            c = criterion(K, smoothness_score="energy")
+            for lname, method in (("gambler", c.gambler_loss), ("smoothness", c.smoothness_loss), ("sparsity", c.sparsity_loss)):
+                pin(f"crop/pebal/{lname}", dense(method, tg), leaves, sums=True)
+    return out
+
+
+def g_criterion(R, check=False):
+    arrs = build_g9(R)
+    if not check:
+        return save("g9_criterion", **arrs)
+    path = os.path.join(HERE, "g9_criterion.npz")
+    with np.load(path) as z:
+        old = {k: z[k] for k in z.files}
+    bad = sorted(set(old) ^ set(arrs)) + [k for k in arrs if k in old and not (
+        old[k].dtype == np.asarray(arrs[k]).dtype and np.array_equal(old[k], arrs[k], equal_nan=old[k].dtype.kind == "f"))]
+    print(f"  g9_criterion: {len(arrs)} arrays regenerated, {len(bad)} differ from the committed file" + "".join("\n    " + k for k in bad[:20]))
+    if bad:
+        sys.exit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
     ap.add_argument("--full", action="store_true")
+    ap.add_argument("--check", action="store_true", help="g9_criterion: regenerate in memory and compare with the committed file; write nothing")
     args = ap.parse_args()
     torch.set_num_threads(8)
     R = _ref_modules()
@@ -581,6 +928,7 @@ def main():
         "g4tiny3": lambda: g_end_to_end(R, "tiny3", 60, 90, 0, 1234, True, "g4_tiny3_60x90"),
         "g4tiny1dh": lambda: g_end_to_end(R, "tiny1_dh", 60, 90, 0, 1234, True, "g4_tiny1_dh_60x90"),
         "g6": lambda: g_metrics(R),
+        "g9_criterion": lambda: g_criterion(R, args.check),
     }
     if args.full:
         jobs["g5c2"] = lambda: g_end_to_end(R, "swin_b_1dl", 1024, 2048, 0, 1234, False, "g5_swin_b_1dl_1024x2048")
