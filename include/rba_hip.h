@@ -52,6 +52,8 @@
  *   rba_confusion_accum         <- Detectron2's SemSegEvaluator.process: np.bincount((K + 1) * pred + gt) per image (train_net.py:96-121 builds it)
  *   rba_train_view_u8           <- MaskFormerSemanticCocoMixDatasetMapper.__call__ behind the decode: mix_object, ResizeShortestEdge, RandomCrop,
  *                                  ColorAugSSDTransform, RandomFlip, the pad and the outlier mask (mask_former_semantic_coco_mix_dataset_mapper.py)
+ *   rba_grad_sqnorm_f32         <- Trainer.build_optimizer's FullModelGradientClippingOptimizer over torch.optim.AdamW: clip_grad_norm_ and the
+ *   rba_clip_adamw_step_f32        AdamW step of every trained tensor (train_net.py:303-328)
  *   rba_swin_window_attn_f32    <- WindowAttention core + window_partition/reverse + roll + pad
  *                                  (backbone/swin.py:44-71, 131-171, 251-284)
  *   rba_skinny_linear_f32       <- nn.Linear / in_proj / MLP on the decoder's [100, B, 256] query tensors
@@ -753,6 +755,43 @@ typedef struct {
   rba_train_view_color color;
 } rba_train_view;
 int rba_train_view_u8(const rba_train_view* view /* host */, void* stream);
+
+/* K15.  The optimizer step of the head fine-tune: torch.nn.utils.clip_grad_norm_(params, max_norm) + torch.optim.AdamW(amsgrad=False).step()
+ * (train_net.py:303-328 of the reference) as two launches over flat fp32 state (docs/kernels/K15.md).  grad, exp_avg and exp_avg_sq are flat buffers of
+ * one layout: tensor t occupies [offset, offset + n), every offset is a multiple of 4 elements and the gaps hold zeros; the buffers are 16-byte
+ * aligned.  The parameters stay where the model has them (element-aligned is enough: a view of a larger tensor).
+ *   K15a  rba_grad_sqnorm_f32: partials[b] = the sum of (grad[i] * grad_scale)^2 over workgroup b's fixed share of [0, n), 1 <= n_partials <=
+ *         RBA_ADAMW_MAX_PARTIALS, every slot written.  No atomics: bitwise reproducible.
+ *   K15b  rba_clip_adamw_step_f32: norm = sqrt(sum of the partials, summed by every workgroup in one fixed order); coef = max_norm / (norm + 1e-6)
+ *         where that is below 1, else 1 (a NaN stays NaN); max_norm <= 0: coef = 1.  stats[0] = norm.  Then for every element of every tensor, with
+ *         lr_t = lr * lr_mult, g = grad * grad_scale * coef:
+ *             p *= 1 - lr_t * weight_decay;  m += (g - m) (1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ *             p -= (lr_t / bias_correction1) * m / (sqrt(v) / bias_correction2_sqrt + eps)
+ *         the two host scalars of torch (1 - lr_t * weight_decay, lr_t / bias_correction1) formed in double and rounded to fp32 once, as torch does.
+ *         grad is not written: it keeps the unclipped, unscaled sum.
+ * tensors: the descriptors on the device; blocks: n_blocks pairs (tensor index, chunk index) on the device, workgroup b steps elements
+ * [chunk index * chunk, + chunk) of its tensor; chunk a multiple of 4.  Both tables are trusted (the caller built them): every pair must name a chunk
+ * that starts inside its tensor, and together they must cover every element once.  A bad scalar or a misaligned buffer returns hipErrorInvalidValue
+ * without a launch.  No workspace besides partials, no synchronisation, no read-back; capturable. */
+#define RBA_ADAMW_MAX_PARTIALS 1024
+typedef struct {
+  float* param;                /* n elements, where the model keeps them */
+  int64_t offset;              /* of the tensor's slice in the flat buffers, a multiple of 4 */
+  int64_t n;
+  double lr_mult;              /* the group's learning rate is lr * lr_mult */
+  double weight_decay;
+} rba_adamw_tensor;
+int rba_grad_sqnorm_f32(const float* grad, int64_t n, float grad_scale, float* partials, int n_partials, void* stream);
+typedef struct {               /* one step's scalars, read on the host */
+  double lr;                   /* of a group with multiplier 1 */
+  double beta1, beta2, eps;
+  double bias_correction1;     /* 1 - beta1^step */
+  double bias_correction2_sqrt; /* sqrt(1 - beta2^step) */
+  float grad_scale, max_norm;
+} rba_adamw_hyper;
+int rba_clip_adamw_step_f32(const rba_adamw_tensor* tensors, const int32_t* blocks /* [n_blocks][2] */, int n_blocks, int chunk, const float* grad,
+                            float* exp_avg, float* exp_avg_sq, const float* partials, int n_partials, const rba_adamw_hyper* hyper /* host */,
+                            float* stats /* [1] */, void* stream);
 
 #ifdef __cplusplus
 }

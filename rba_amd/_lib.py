@@ -64,6 +64,8 @@ SIGNATURES = {
     "rba_resize_u8_pil_bilinear": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
     "rba_confusion_accum": [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp],
     "rba_train_view_u8": [_vp, _vp],
+    "rba_grad_sqnorm_f32": [_vp, _i64, ctypes.c_float, _vp, _i, _vp],
+    "rba_clip_adamw_step_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "rba_swin_window_attn_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_window_attn_split_out_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_swin_bias_fragments_elems": [_i, _i],
@@ -152,7 +154,22 @@ class TrainView(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in TRAIN_VIEW_POINTERS] + [(n, ctypes.c_int) for n in TRAIN_VIEW_INTS] + [("color", TrainViewColor)])
 
 
-EXPECTED_ABI = 191       # rba_hip_version() the argtypes above were written for (include/rba_hip.h)
+ADAMW_MAX_PARTIALS = 1024     # RBA_ADAMW_MAX_PARTIALS
+
+
+class AdamWTensor(ctypes.Structure):
+    """rba_adamw_tensor of include/rba_hip.h"""
+    _fields_ = [("param", ctypes.c_void_p), ("offset", ctypes.c_int64), ("n", ctypes.c_int64), ("lr_mult", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
+
+
+class AdamWHyper(ctypes.Structure):
+    """rba_adamw_hyper of include/rba_hip.h"""
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "bias_correction1", "bias_correction2_sqrt")] + \
+               [("grad_scale", ctypes.c_float), ("max_norm", ctypes.c_float)]
+
+
+EXPECTED_ABI = 191      # rba_hip_version() the argtypes above were written for (include/rba_hip.h)
 
 _lib = None
 

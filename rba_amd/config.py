@@ -93,7 +93,18 @@ _DEFAULTS = {
               "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9], "SINGLE_CATEGORY_MAX_AREA": 1.0},
               "DATASET_MAPPER_NAME": "mask_former_semantic", "COLOR_AUG_SSD": False, "SIZE_DIVISIBILITY": -1,
               "OOD_LABEL": 254, "OOD_PROB": 0.2, "COCO_ROOT": "coco/", "COCO_PROXY_SIZE": 300, "REPEAT_INSTANCE_MASKS": 1},
-    "SOLVER": {"FORCE_REGION_PARTITION": False},
+    # the keys rba_amd.solver and rba_amd.train_net read.  Detectron2 is not installed here, so its defaults (detectron2/config/defaults.py SOLVER and the
+    # DeepLab project's add_deeplab_config: POLY_LR_POWER, POLY_LR_CONSTANT_ENDING) are RESTATED, their parity unpinned; WEIGHT_DECAY_EMBED, OPTIMIZER and
+    # BACKBONE_MULTIPLIER are add_maskformer2_config's (mask2former/config.py:24-27).  The Cityscapes base config sets IMS_PER_BATCH 16, BASE_LR 1e-4,
+    # MAX_ITER 90000, WARMUP_FACTOR 1.0, WARMUP_ITERS 0, WEIGHT_DECAY 0.05, ADAMW, WarmupPolyLR, full_model clipping at 0.01 and AMP
+    # (tests/golden/solver/base_solver.yaml)
+    "SOLVER": {"FORCE_REGION_PARTITION": False,
+               "LR_SCHEDULER_NAME": "WarmupMultiStepLR", "MAX_ITER": 40000, "BASE_LR": 0.001, "WEIGHT_DECAY": 0.0001, "WEIGHT_DECAY_NORM": 0.0,
+               "WEIGHT_DECAY_EMBED": 0.0, "OPTIMIZER": "ADAMW", "BACKBONE_MULTIPLIER": 0.1, "MOMENTUM": 0.9,
+               "WARMUP_FACTOR": 0.001, "WARMUP_ITERS": 1000, "WARMUP_METHOD": "linear", "POLY_LR_POWER": 0.9, "POLY_LR_CONSTANT_ENDING": 0.0,
+               "CHECKPOINT_PERIOD": 5000, "IMS_PER_BATCH": 16,
+               "CLIP_GRADIENTS": {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0},
+               "AMP": {"ENABLED": False}},
     # detectron2/config/defaults.py TEST.AUG (rba_amd.test_time_augmentation); the Cityscapes base config sets [512 .. 1792], 4096, FLIP
     "TEST": {"AUG": {"ENABLED": False, "MIN_SIZES": [400, 500, 600, 700, 800, 900, 1000, 1100, 1200], "MAX_SIZE": 4000, "FLIP": True}},
 }

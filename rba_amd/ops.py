@@ -511,6 +511,112 @@ def train_view(img, lab, params, obj=None, objmask=None, lut=None, ignore_label=
     return image, sem_seg, outlier_mask, hist
 
 
+# K15's launch rule (csrc/adamw_step.hip): 256 threads; K15a gives one workgroup ADAMW_SHARE flat elements until ADAMW_MAX_PARTIALS workgroups are reached,
+# then equal larger shares; K15b's workgroup steps one chunk of one tensor: ADAMW_CHUNK elements (one 16-byte access per thread and array) while the
+# whole state has at most ADAMW_SMALL elements -- the step is launch-bound there and many short workgroups finish soonest -- else ADAMW_CHUNK_LARGE
+# (every workgroup re-sums the partials: up to 4 KiB, amortised over 448 KiB of state traffic)
+ADAMW_THREADS, ADAMW_SHARE, ADAMW_MAX_PARTIALS, ADAMW_CHUNK, ADAMW_CHUNK_LARGE, ADAMW_SMALL = 256, 4096, _lib.ADAMW_MAX_PARTIALS, 1024, 16384, 1 << 20
+
+
+class AdamWPlan:
+    """What K15 needs besides the three flat buffers, built once per optimizer by `adamw_plan`: the parameters (kept alive: the device table holds
+    their raw pointers), each one's slice [offset, offset + n) of the flat layout, the two device tables, the partials and the one-float stats."""
+    __slots__ = ("params", "ptrs", "offsets", "sizes", "total", "chunk", "n_blocks", "n_partials", "tensors", "blocks", "partials", "stats", "device")
+
+
+def adamw_flat(plan_or_total, device=None):
+    """A zeroed flat fp32 buffer of K15's layout (grad, exp_avg or exp_avg_sq): the gaps between the slices must hold zeros, and stay zero."""
+    total, device = (plan_or_total.total, plan_or_total.device) if isinstance(plan_or_total, AdamWPlan) else (int(plan_or_total), device)
+    return torch.zeros(total, dtype=torch.float32, device=device)
+
+
+@_hip_op
+def adamw_plan(params, lr_mults, weight_decays, chunk=None):
+    """K15's tables for `params` (fp32 HIP tensors, contiguous, at least one element each; views of larger tensors are fine), with the per-tensor
+    learning-rate multiplier and weight decay -> AdamWPlan.  Slices are laid out in the order given, each starting on a multiple of four elements.
+    ``chunk``: elements per workgroup of K15b (a multiple of 4), by the launch rule above when None.  Built and uploaded here, once."""
+    params = list(params)
+    if not params or len(lr_mults) != len(params) or len(weight_decays) != len(params):
+        raise RbaHipError("adamw_plan needs at least one parameter and one lr multiplier and one weight decay per parameter")
+    for i, p_ in enumerate(params):
+        _chk(p_, f"params[{i}]")
+        if p_.numel() < 1:
+            raise RbaHipError(f"params[{i}] is empty")
+    if len({p_.data_ptr() for p_ in params}) != len(params):
+        raise RbaHipError("adamw_plan: a parameter is listed twice")
+    plan = AdamWPlan()
+    plan.params, plan.device = params, params[0].device
+    plan.ptrs = [p_.data_ptr() for p_ in params]
+    plan.sizes = [p_.numel() for p_ in params]
+    plan.offsets, at = [], 0
+    for n in plan.sizes:
+        plan.offsets.append(at)
+        at += (n + 3) // 4 * 4
+    plan.total = at
+    plan.chunk = int(chunk) if chunk is not None else (ADAMW_CHUNK if at <= ADAMW_SMALL else ADAMW_CHUNK_LARGE)
+    if plan.chunk < 4 or plan.chunk % 4:
+        raise RbaHipError(f"adamw_plan: chunk must be a positive multiple of 4, got {plan.chunk}")
+    pairs = [(t, c) for t, n in enumerate(plan.sizes) for c in range((n + plan.chunk - 1) // plan.chunk)]
+    plan.n_blocks = len(pairs)
+    if plan.n_blocks >= 1 << 31:
+        raise RbaHipError(f"adamw_plan: {plan.n_blocks} chunks of {plan.chunk} elements exceed one launch's grid; pass a larger chunk")
+    plan.n_partials = max(1, min(ADAMW_MAX_PARTIALS, (at + ADAMW_SHARE - 1) // ADAMW_SHARE))
+    table = (_lib.AdamWTensor * len(params))()
+    for d, ptr, off, n, m, wd in zip(table, plan.ptrs, plan.offsets, plan.sizes, lr_mults, weight_decays):
+        d.param, d.offset, d.n, d.lr_mult, d.weight_decay = ptr, off, n, float(m), float(wd)
+    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8)
+    plan.tensors = torch.empty(host.numel(), dtype=torch.uint8, device=plan.device)
+    plan.tensors.copy_(host)
+    plan.blocks = torch.empty((plan.n_blocks, 2), dtype=torch.int32, device=plan.device)
+    plan.blocks.copy_(torch.tensor(pairs, dtype=torch.int32))
+    plan.partials = torch.empty(plan.n_partials, dtype=torch.float32, device=plan.device)
+    plan.stats = torch.zeros(1, dtype=torch.float32, device=plan.device)
+    return plan
+
+
+def _adamw_flat_ok(plan, t, name):
+    """A flat buffer of `plan`'s layout: fp32, exactly plan.total elements, on the plan's device, 16-byte aligned."""
+    if not isinstance(plan, AdamWPlan):
+        raise RbaHipError("plan must be an AdamWPlan (ops.adamw_plan)")
+    _vec(t, name, plan.total)
+    if t.device != plan.device or t.data_ptr() % 16:
+        raise RbaHipError(f"{name} must be on {plan.device} and 16-byte aligned")
+    return t
+
+
+@_hip_op
+def grad_sqnorm(plan, grad, grad_scale=1.0):
+    """K15a.  plan.partials[b] = the sum of (grad * grad_scale)^2 over workgroup b's share of the flat gradient buffer, every slot written, in a fixed
+    order (bitwise reproducible) -> plan.partials.  Nothing is read back."""
+    _adamw_flat_ok(plan, grad, "grad")
+    _launch("rba_grad_sqnorm_f32", grad.data_ptr(), plan.total, float(grad_scale), plan.partials.data_ptr(), plan.n_partials)
+    return plan.partials
+
+
+@_hip_op
+def clip_adamw_step(plan, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=0.0, grad_scale=1.0):
+    """K15b, after `grad_sqnorm` with the same grad and grad_scale.  Step number ``step`` (1 for the first) of torch.optim.AdamW(amsgrad=False) on every
+    parameter of the plan, in place, behind clip_grad_norm_(params, max_norm) (max_norm <= 0: no clipping) of grad * grad_scale; ``lr`` is the learning
+    rate of a group with multiplier 1.  exp_avg and exp_avg_sq are updated in place, grad is left as it is, plan.stats[0] receives the gradient norm.
+    The bias corrections are formed here in double, as torch forms them.  The parameters are written through raw pointers: every one's version counter
+    is raised here, so that the caches keyed on it see the step.  A parameter whose storage moved since the plan was built raises.  Nothing is read
+    back and nothing synchronises."""
+    _adamw_flat_ok(plan, grad, "grad")
+    _adamw_flat_ok(plan, exp_avg, "exp_avg")
+    _adamw_flat_ok(plan, exp_avg_sq, "exp_avg_sq")
+    step, (beta1, beta2) = int(step), (float(b) for b in betas)
+    if step < 1 or not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0) or eps < 0.0:
+        raise RbaHipError(f"clip_adamw_step needs step >= 1, betas in [0, 1) and eps >= 0, got step {step}, betas {(beta1, beta2)}, eps {eps}")
+    for i, (p_, ptr, n) in enumerate(zip(plan.params, plan.ptrs, plan.sizes)):
+        if p_.data_ptr() != ptr or p_.numel() != n:
+            raise RbaHipError(f"clip_adamw_step: parameter {i} of the plan was moved or resized since adamw_plan; build a new plan")
+    h = _lib.AdamWHyper(lr=float(lr), beta1=beta1, beta2=beta2, eps=float(eps), bias_correction1=1.0 - beta1 ** step,
+                        bias_correction2_sqrt=(1.0 - beta2 ** step) ** 0.5, grad_scale=float(grad_scale), max_norm=float(max_norm))
+    _launch("rba_clip_adamw_step_f32", plan.tensors.data_ptr(), plan.blocks.data_ptr(), plan.n_blocks, plan.chunk, grad.data_ptr(), exp_avg.data_ptr(),
+            exp_avg_sq.data_ptr(), plan.partials.data_ptr(), plan.n_partials, ctypes.addressof(h), plan.stats.data_ptr())
+    torch.autograd.graph.increment_version(plan.params)
+
+
 # K13's launch rule (csrc/confusion.hip), for tests that size a map to a number of sweeps of the capped grid
 CONFUSION_THREADS, CONFUSION_TILE, CONFUSION_GRID_CAP, CONFUSION_LDS_MAX_K = 256, 16, 512, 126
 
