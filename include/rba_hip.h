@@ -29,6 +29,7 @@
  *                                  (maskformer_model.py:294-299, msdeformattn.py:358, mask2former_transformer_decoder.py:483)
  *   rba_masked_xattn_f32        <- nn.MultiheadAttention core with bool attn_mask
  *                                  (mask2former_transformer_decoder.py:106-118, 433, 483-487)
+ *   rba_masked_xattn_bwd_f32    <- autograd's backward of that core (the whole-decoder fine-tune of the PEBAL recipe)
  *   rba_mask_logits_f32         <- torch.einsum("bqc,bchw->bqhw") (mask2former_transformer_decoder.py:479)
  *   rba_mask_logits_f16x3_f32   <- the same call site, f16x3 arithmetic
  *   rba_mask_logits_bwd_f32     <- autograd's backward of that einsum (mask2former_transformer_decoder.py:479 under autograd)
@@ -195,6 +196,25 @@ int rba_msda_fused_f32(const float* value, const int64_t* spatial_shapes, const 
 int64_t rba_masked_xattn_workspace_bytes(int B, int Q, int S, int nH);
 int rba_masked_xattn_f32(const float* q, const float* k, const float* v, const float* mask_logits, float* out,
                          float* workspace, int B, int Q, int S, int nH, int hd, void* stream);
+
+/* K3 backward.  Gradients of the op above with respect to q, k and v, given grad_out [B,Q,nH*hd] = d loss / d out.  Inputs exactly as the
+ * forward's (q unscaled); mask_logits [B,Q,S] or NULL receives no gradient (the reference detaches it, mask2former_transformer_decoder.py:487).
+ * Mask rule bit for bit the forward's: a pair is blocked iff mask_logits <= -0x1.7ffffep-23 (torch's fp32 sigmoid(x) < 0.5), a row whose keys
+ * are all blocked attends to every key; a blocked (query, key) pair contributes exactly nothing to any gradient.
+ *   s = hd^-0.5 q.k, p = softmax over the row's un-blocked keys, dp = grad_out.v, delta = sum_s p dp
+ *   grad_v[s] = sum_q p grad_out[q]     ds = p (dp - delta) hd^-0.5     grad_k[s] = sum_q ds q     grad_q[q] = sum_s ds k[s]
+ * Flash-style: the row statistics are recomputed, nothing of size [B*nH,Q,S] is written.  Exact fp32 FMA, no half-precision operand.
+ * grad_q [B,Q,nH,hd], grad_k and grad_v [B,S,nH,hd] are each optional (NULL = not wanted and not computed; all three NULL is a no-op).  Every
+ * requested output is written element by element with plain stores, whatever it held before, by ONE writer in a fixed summation order: all
+ * three are bitwise reproducible from launch to launch (no float atomics, no hand-off between workgroups: grad_q is summed by the workgroup
+ * that owns the whole query row).  `workspace`: device memory owned by the caller, 16-byte aligned, rba_masked_xattn_bwd_workspace_bytes
+ * bytes (the row statistics; its contents on entry do not matter), required whenever a kernel is launched.  k, v, grad_k, grad_v 16-byte
+ * aligned.  hd must be 32; S >= 1; 0 <= B, nH <= 65535; Q >= 0 (any, also > 128).  B == 0: success without a launch.  Q == 0: grad_k / grad_v
+ * are zero-filled (hipMemsetAsync on `stream`), no kernel.  Anything else returns hipErrorInvalidValue without a launch. */
+int64_t rba_masked_xattn_bwd_workspace_bytes(int B, int Q, int S, int nH);
+int rba_masked_xattn_bwd_f32(const float* q, const float* k, const float* v, const float* mask_logits, const float* grad_out,
+                             float* grad_q /* or NULL */, float* grad_k /* or NULL */, float* grad_v /* or NULL */, float* workspace,
+                             int B, int Q, int S, int nH, int hd, void* stream);
 
 /* K4.  Mask logits: out[b,q,n] = sum_c embed[b,q,c] * feat[b,c,n]   (embed [B,Q,C], feat [B,C,N], out [B,Q,N]). */
 int rba_mask_logits_f32(const float* embed, const float* feat, float* out, int B, int Q, int C, int64_t N,

@@ -37,6 +37,8 @@ SIGNATURES = {
     "rba_msda_fused_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_masked_xattn_workspace_bytes": [_i, _i, _i, _i],
     "rba_masked_xattn_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "rba_masked_xattn_bwd_workspace_bytes": [_i, _i, _i, _i],
+    "rba_masked_xattn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_mask_logits_f32": [_vp, _vp, _vp, _i, _i, _i, _i64, _vp],
     "rba_mask_logits_f16x3_f32": [_vp, _vp, _vp, _i, _i, _i, _i64, _vp],
     "rba_mask_logits_bwd_workspace_f32": [_i, _i, _i, _i64, _vp],

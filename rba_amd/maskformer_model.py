@@ -122,13 +122,17 @@ class MaskFormer(nn.Module):
         (``criterion.outlier_loss(outputs, targets)["outlier_loss"].backward()``); with the predictor's ``deep_supervision`` set too, so does every
         ``aux_outputs`` entry.  On a model with the DenseHybrid head, ``outputs["ood_pred"]`` [B,2,H/4,W/4] is the inference kernel's output without
         a graph, or -- with the predictor's ``differentiable_ood_head`` set -- the head in plain torch with a graph over its four parameters
-        (``criterion.densehybrid_loss(outputs, targets, num_classes=K)["densehybrid_loss"].backward()``).  Eager launches only: graph replay is never
-        used here."""
+        (``criterion.densehybrid_loss(outputs, targets, num_classes=K)["densehybrid_loss"].backward()``).  With the predictor's
+        ``differentiable_decoder`` set too, the graph also covers the decoder layers and the three embeddings (the released PEBAL recipe; see
+        ``MultiScaleMaskedTransformerDecoder``).  Eager launches only: graph replay is never used here."""
         predictor = self.sem_seg_head.predictor
         if not getattr(predictor, "differentiable_heads", False):
             if getattr(predictor, "deep_supervision", False):
                 raise ops.RbaHipError("finetune_outputs: predictor.deep_supervision is set without predictor.differentiable_heads; deep supervision "
                                       "is the differentiable heads' aux_outputs, so set differentiable_heads = True as well")
+            if getattr(predictor, "differentiable_decoder", False):
+                raise ops.RbaHipError("finetune_outputs: predictor.differentiable_decoder is set without predictor.differentiable_heads; the decoder "
+                                      "layers' graph hangs off the differentiable head calls, so set differentiable_heads = True as well")
             raise ops.RbaHipError("finetune_outputs: set model.sem_seg_head.predictor.differentiable_heads = True first (without it the outputs "
                                   "carry no autograd graph)")
         with torch.no_grad():

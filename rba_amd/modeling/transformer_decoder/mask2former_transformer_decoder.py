@@ -65,6 +65,32 @@ class MaskLogitsFunction(Function):
         return ops.mask_logits_backward(embed, feat, grad_out, need_embed=need_embed, need_feat=need_feat)
 
 
+class MaskedXattnFunction(Function):
+    """``MaskedXattnFunction.apply(q [B,Q,nH,32], k, v [B,S,nH,32], mask_logits [B,Q,S] | None) -> [B,Q,nH*32]``: ``ops.masked_xattn`` (the very
+    bits of a direct call), differentiable once with respect to q, k and v through K3's backward kernel (``ops.masked_xattn_backward``).  The mask
+    logits get no gradient (the reference detaches them, :487).  The backward reads all three tensors and the mask whatever is asked for, so they
+    are saved only when some gradient is; a gradient nobody asks for is not computed."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask_logits):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if mask_logits is not None:
+            mask_logits = mask_logits.contiguous()
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(q, k, v, mask_logits)
+        return ops.masked_xattn(q, k, v, mask_logits)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        need = ctx.needs_input_grad[:3]
+        if not any(need):
+            return None, None, None, None
+        q, k, v, mask_logits = ctx.saved_tensors
+        grad_out = grad_out.contiguous()                     # `out.sum().backward()` hands an expanded (stride 0) gradient
+        return ops.masked_xattn_backward(q, k, v, mask_logits, grad_out, *need) + (None,)
+
+
 class _HeadLayerNormFunction(Function):
     """``decoder_norm`` of the differentiable last head call: forward = the kernel of the inference path (``ops.add_layer_norm``), backward = torch's
     LayerNorm backward on the [B*Q, C] query tensor, for weight and bias only -- the decoder-layer output receives no gradient."""
@@ -109,6 +135,112 @@ class _HeadLinearFunction(Function):
         return gx, gw, g.sum(0) if ctx.needs_input_grad[2] else None, None
 
 
+# ------------------------------------------------------------------------------------------------ the differentiable decoder layers
+# (``MultiScaleMaskedTransformerDecoder.differentiable_decoder``): every forward below is the inference path's launch, so the values are its
+# bits; the backwards are small library GEMMs on [B*Q, C] rows by design, as `_HeadLinearFunction`'s, and K3's backward kernel for the core.
+def _rows(t):
+    return t.reshape(-1, t.shape[-1])
+
+
+class _LinearFunction(Function):
+    """``_qlinear(x, weight, bias, relu, x_add)`` with gradients for x, x_add (the position embedding: the same rows as x's), weight and bias."""
+
+    @staticmethod
+    def forward(ctx, x, x_add, weight, bias, relu):
+        y = _qlinear(x, weight, bias, relu, x_add)
+        ctx.relu = relu
+        ctx.save_for_backward(x, x_add, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, x_add, weight, y = ctx.saved_tensors
+        g = _rows(grad_y)
+        if ctx.relu:
+            g = g * (_rows(y) > 0)
+        need = ctx.needs_input_grad
+        gx = (g @ weight).view(x.shape) if need[0] or need[1] else None
+        gw = g.t() @ _rows(x if x_add is None else x + x_add) if need[2] else None
+        return gx if need[0] else None, gx if need[1] else None, gw, g.sum(0) if need[3] else None, None
+
+
+class _QKVFunction(Function):
+    """Self-attention's stacked in_proj in one launch (``ops.skinny_linear(..., add_cols=2E, segments=3)``): q, k from x + x_add, v from x."""
+
+    @staticmethod
+    def forward(ctx, x, x_add, weight, bias):
+        E = weight.shape[1]
+        ctx.save_for_backward(x, x_add, weight)
+        return tuple(ops.skinny_linear(x, weight, bias, x_add=None if x_add is None else x_add.contiguous(), add_cols=2 * E, segments=3))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gq, gk, gv):
+        x, x_add, weight = ctx.saved_tensors
+        E = weight.shape[1]
+        gqk, gv = torch.cat((_rows(gq), _rows(gk)), 1), _rows(gv)
+        need = ctx.needs_input_grad
+        ga = (gqk @ weight[:2 * E]).view(x.shape) if need[0] or need[1] else None
+        gx = ga + (gv @ weight[2 * E:]).view(x.shape) if need[0] else None
+        gw = torch.cat((gqk.t() @ _rows(x if x_add is None else x + x_add), gv.t() @ _rows(x)), 0) if need[2] else None
+        gb = torch.cat((gqk.sum(0), gv.sum(0))) if need[3] else None
+        return gx, ga if need[1] else None, gw, gb
+
+
+class _KVFunction(Function):
+    """The key / value projections of `_MHAParams._project_kv` (k from key + key_add, v from key) with gradients for key, key_add, the stacked
+    in_proj weight and bias (their q rows get zeros) and for `level_row` [C]: a vector that the caller has ALREADY added to every row of `key`
+    (``level_embed.weight[i]`` inside the detached memory) -- its gradient is (sum_s dk_s) W_k + (sum_s dv_s) W_v, no d key [B,S,C] needed."""
+
+    @staticmethod
+    def forward(ctx, mha, key, key_add, level_row, weight, bias):
+        ctx.save_for_backward(key, key_add, weight)
+        return mha._project_kv(key, key, key_add)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gk, gv):
+        key, key_add, weight = ctx.saved_tensors
+        E = weight.shape[1]
+        gk, gv = _rows(gk.reshape(key.shape)), _rows(gv.reshape(key.shape))
+        wk, wv = weight[E:2 * E], weight[2 * E:]
+        _, need_key, need_add, need_level, need_w, need_b = ctx.needs_input_grad
+        ga = (gk @ wk).view(key.shape) if need_key or need_add else None
+        gkey = ga + (gv @ wv).view(key.shape) if need_key else None
+        sk, sv = (gk.sum(0), gv.sum(0)) if need_level or need_b else (None, None)
+        glevel = sk @ wk + sv @ wv if need_level else None
+        gw = torch.cat((weight.new_zeros(E, E), gk.t() @ _rows(key if key_add is None else key + key_add), gv.t() @ _rows(key)), 0) if need_w else None
+        gb = torch.cat((sk.new_zeros(E), sk, sv)) if need_b else None
+        return None, gkey, ga if need_add else None, glevel, gw, gb
+
+
+class _AddLayerNormFunction(Function):
+    """``ops.add_layer_norm(x, weight, bias, eps, residual, residual_bias)[1]`` = LayerNorm(x + residual + residual_bias) with gradients for x,
+    residual, the folded bias (out_proj.bias / linear2.bias), weight and bias: torch's LayerNorm backward on the [B*Q, C] rows."""
+
+    @staticmethod
+    def forward(ctx, x, residual, residual_bias, weight, bias, eps):
+        ctx.eps = eps
+        s, y = ops.add_layer_norm(x, weight, bias, eps, residual, residual_bias)
+        ctx.save_for_backward(s, weight, bias)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        s, weight, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_s = need[0] or need[1] or need[2]
+        with torch.enable_grad():
+            z = s.detach().requires_grad_(need_s)
+            w, b = weight.detach().requires_grad_(True), bias.detach().requires_grad_(True)
+            y = F.layer_norm(z, (z.shape[-1],), w, b, ctx.eps)
+        gs, gw, gb = torch.autograd.grad(y, (z, w, b), grad_y) if need_s else (None,) + torch.autograd.grad(y, (w, b), grad_y)
+        return (gs if need[0] else None, gs if need[1] else None, _rows(gs).sum(0) if need[2] else None,
+                gw if need[3] else None, gb if need[4] else None, None)
+
+
 class _MHAParams(nn.Module):
     """Parameter holder with nn.MultiheadAttention's names: in_proj_weight, in_proj_bias, out_proj.{weight,bias}."""
 
@@ -140,29 +272,48 @@ class _MHAParams(nn.Module):
             o = ops.masked_xattn(q.view(B, Q, nH, E // nH), k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH), mask_logits)
             return _qlinear(o, self.out_proj.weight)
         q = _qlinear(query, w[:E], b[:E], x_add=query_add).view(B, Q, nH, E // nH)
+        k, v = self._project_kv(key, value, key_add)
+        o = ops.masked_xattn(q, k, v, mask_logits)
+        return _qlinear(o, self.out_proj.weight)            # out_proj.bias is added inside the caller's fused add+LN
+
+    def _project_kv(self, key, value, key_add):
+        """k = W_k (key + key_add) + b_k, v = W_v value + b_v as [B,S,nH,hd], by the kernel that pays for the shape"""
+        E, nH = self.embed_dim, self.num_heads
+        B, S, _ = key.shape
+        w, b = self.in_proj_weight, self.in_proj_bias
         if (key is value and B * S > 128 and key.is_contiguous() and ops.token_linear_pays(B * S, E, E)
                 and (key_add is None or (key_add.is_contiguous() and tuple(key_add.shape) == tuple(key.shape)))):
             # cross-attention: k = W_k (memory + pos) + b_k and v = W_v memory + b_v in ONE launch of the row-complete kernel (was: an add and two
             # library GEMMs per layer)
             lk, lv = self._kv_views()
             k, v = ops.token_linear_multi(key, [(lk, key_add, None, 0, False), (lv, None, None, 0, False)])
-            o = ops.masked_xattn(q, k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH), mask_logits)
-            return _qlinear(o, self.out_proj.weight)
+            return k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH)
         if key_add is not None:
             key = key + key_add
         if B * S > 128:
             # a memory level beyond the row-complete kernel's range (C5's 14 400-token level): the key / value projections are ordinary token
             # Linears -> K6 where it pays (ops.linear decides; the packed planes are cached on the views), not a library GEMM
             lk, lv = self._kv_views()
-            k = ops.linear(key.contiguous(), lk).view(B, S, nH, E // nH)
-            v = ops.linear(value.contiguous(), lv).view(B, S, nH, E // nH)
-            o = ops.masked_xattn(q, k, v, mask_logits)
-            return _qlinear(o, self.out_proj.weight)
+            return ops.linear(key.contiguous(), lk).view(B, S, nH, E // nH), ops.linear(value.contiguous(), lv).view(B, S, nH, E // nH)
         # self-attention: key / value are the (<= 128) queries themselves -> the skinny kernel too (hipBLASLt takes 33 us for 100 x 256 x 256)
-        k = _qlinear(key, w[E:2 * E], b[E:2 * E]).view(B, S, nH, E // nH)
-        v = _qlinear(value, w[2 * E:], b[2 * E:]).view(B, S, nH, E // nH)
-        o = ops.masked_xattn(q, k, v, mask_logits)
-        return _qlinear(o, self.out_proj.weight)            # out_proj.bias is added inside the caller's fused add+LN
+        return _qlinear(key, w[E:2 * E], b[E:2 * E]).view(B, S, nH, E // nH), _qlinear(value, w[2 * E:], b[2 * E:]).view(B, S, nH, E // nH)
+
+    def forward_differentiable(self, query, key, mask_logits=None, key_add=None, query_add=None, level_row=None):
+        """`forward(query, key, key, ...)` -- the same launches in the same order, the same bits -- with an autograd graph over query, key, the
+        position operands and the four parameters; the mask logits get no gradient.  level_row: see `_KVFunction`."""
+        E, nH = self.embed_dim, self.num_heads
+        B, Q, _ = query.shape
+        S = key.shape[1]
+        w, b = self.in_proj_weight, self.in_proj_bias
+        if (query is key and key_add is query_add and B * Q <= 128 and E % 32 == 0 and E % 16 == 0
+                and w.is_contiguous() and query.is_contiguous()):
+            q, k, v = _QKVFunction.apply(query, query_add, w, b)
+            k, v = k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH)
+        else:
+            q = _LinearFunction.apply(query, query_add, w[:E], b[:E], False)
+            k, v = _KVFunction.apply(self, key, key_add, level_row, w, b)
+        o = MaskedXattnFunction.apply(q.view(B, Q, nH, E // nH), k, v, mask_logits)
+        return _LinearFunction.apply(o, None, self.out_proj.weight, None, False)
 
 
 class SelfAttentionLayer(nn.Module):
@@ -177,6 +328,12 @@ class SelfAttentionLayer(nn.Module):
         return ops.add_layer_norm(tgt.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps, t2,
                                   self.self_attn.out_proj.bias)[1]          # forward_post :48-58
 
+    def forward_differentiable(self, tgt, query_pos):
+        """forward's launches and bits, with an autograd graph over tgt, query_pos and the layer's parameters"""
+        tgt = tgt.contiguous()
+        t2 = self.self_attn.forward_differentiable(tgt, tgt, key_add=query_pos, query_add=query_pos)
+        return _AddLayerNormFunction.apply(tgt, t2, self.self_attn.out_proj.bias, self.norm.weight, self.norm.bias, self.norm.eps)
+
 
 class CrossAttentionLayer(nn.Module):
     def __init__(self, d_model, nhead):
@@ -188,6 +345,13 @@ class CrossAttentionLayer(nn.Module):
         t2 = self.multihead_attn(tgt, memory, memory, mask_logits, key_add=pos, query_add=query_pos)
         return ops.add_layer_norm(tgt.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps, t2,
                                   self.multihead_attn.out_proj.bias)[1]     # forward_post :106-118
+
+    def forward_differentiable(self, tgt, memory, mask_logits, pos, query_pos, level_row=None):
+        """forward's launches and bits, with an autograd graph over tgt, query_pos and the layer's parameters (memory too where it requires grad);
+        level_row: a vector already added to every row of `memory` that is to receive its gradient (`_KVFunction`)"""
+        m = self.multihead_attn
+        t2 = m.forward_differentiable(tgt, memory, mask_logits, key_add=pos, query_add=query_pos, level_row=level_row)
+        return _AddLayerNormFunction.apply(tgt.contiguous(), t2, m.out_proj.bias, self.norm.weight, self.norm.bias, self.norm.eps)
 
 
 class FFNLayer(nn.Module):
@@ -201,6 +365,12 @@ class FFNLayer(nn.Module):
         t2 = _qlinear(_qlinear(tgt, self.linear1.weight, self.linear1.bias, relu=True), self.linear2.weight)
         return ops.add_layer_norm(tgt.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps, t2,
                                   self.linear2.bias)[1]                     # forward_post :171-175
+
+    def forward_differentiable(self, tgt):
+        """forward's launches and bits, with an autograd graph over tgt and the layer's parameters"""
+        h = _LinearFunction.apply(tgt, None, self.linear1.weight, self.linear1.bias, True)
+        t2 = _LinearFunction.apply(h, None, self.linear2.weight, None, False)
+        return _AddLayerNormFunction.apply(tgt.contiguous(), t2, self.linear2.bias, self.norm.weight, self.norm.bias, self.norm.eps)
 
 
 class MLP(nn.Module):
@@ -266,11 +436,21 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
     DenseHybrid head) is the DenseHybrid recipe's FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP_AND_OOD_PRED: ``out["ood_pred"]`` is then computed in plain
     torch on the detached ``mask_features`` (``BNReluConv.forward_differentiable``) and carries a graph over the head's four parameters --
     ``ood_pred.norm.{weight,bias}``, ``ood_pred.conv.{weight,bias}`` -- and nothing else; the batch norm runs in the mode ``ood_pred.norm.training``
-    says and updates its running statistics in training mode.  Without it ``ood_pred`` stays the inference kernel's output under ``no_grad``."""
+    says and updates its running statistics in training mode.  Without it ``ood_pred`` stays the inference kernel's output under ``no_grad``.
+
+    ``differentiable_decoder`` (attribute, default False; read only with ``differentiable_heads`` set and grad mode on) trains the whole decoder --
+    the released PEBAL recipe, which freezes the backbone and the pixel decoder and nothing else: ``_decode_differentiable`` runs the decoder layers
+    with an autograd graph over every predictor parameter that requires grad (cross-attention, self-attention, FFN, their norms, ``query_feat``,
+    ``query_embed``, ``level_embed``) and the head calls that return outputs are differentiable with respect to the layer output too.  The forward
+    launches the inference kernels in the inference order (``pred_logits``, ``pred_masks`` and the ``aux_outputs`` are the bits of an inference
+    forward with ``sparse_intermediate_heads = False``); the attention core's backward is K3's backward kernel, the Linears' and norms' are library
+    GEMMs / torch's LayerNorm backward on [B*Q, C] rows.  The memory and ``mask_features`` are detached (frozen pixel decoder), the attention-mask
+    logits get no gradient (reference :487) and their head calls stay sparse under ``no_grad``; the cached initial head call is bypassed."""
 
     differentiable_heads = False
     deep_supervision = False
     differentiable_ood_head = False
+    differentiable_decoder = False
     # forward() accepts the pixel decoder's DeferredMaskFeatures in place of the mask-feature tensor (MaskFormerHead asks for one when this is set)
     takes_deferred_mask_features = True
 
@@ -365,22 +545,27 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         dec = ops.add_layer_norm(output.contiguous(), self.decoder_norm.weight, self.decoder_norm.bias, self.decoder_norm.eps)[1]
         return _qlinear(dec, self.class_embed.weight, self.class_embed.bias), self.mask_embed(dec).contiguous()
 
-    def _query_side_heads_differentiable(self, output):
-        """_query_side_heads with an autograd graph over its ten parameters (not over `output`): the same launches in the same order"""
+    def _query_side_heads_differentiable(self, output, through=False):
+        """_query_side_heads with an autograd graph over its ten parameters (not over `output` unless `through`: the differentiable decoder):
+        the same launches in the same order"""
         n = self.decoder_norm
-        dec = _HeadLayerNormFunction.apply(output.detach().contiguous(), n.weight, n.bias, n.eps)
+        if through:
+            dec = _AddLayerNormFunction.apply(output.contiguous(), None, None, n.weight, n.bias, n.eps)
+        else:
+            dec = _HeadLayerNormFunction.apply(output.detach().contiguous(), n.weight, n.bias, n.eps)
         outputs_class = _HeadLinearFunction.apply(dec, self.class_embed.weight, self.class_embed.bias, False)
         e = dec
         for i, layer in enumerate(self.mask_embed.layers):
             e = _HeadLinearFunction.apply(e, layer.weight, layer.bias, i < self.mask_embed.num_layers - 1)
         return outputs_class, e.contiguous()
 
-    def _aux_heads_differentiable(self, outputs, mask_features):
+    def _aux_heads_differentiable(self, outputs, mask_features, through=False):
         """The intermediate head calls of deep supervision on `outputs` = the decoder-layer outputs [B,Q,C] entering them: the query side once on
         their concatenation along the batch axis (row-wise kernels: the bits of one call each, and one backward pass), then one contraction per
-        call against the one `mask_features` -> [{"pred_logits", "pred_masks"}], every tensor with a graph over the ten head tensors only."""
+        call against the one `mask_features` -> [{"pred_logits", "pred_masks"}], every tensor with a graph over the ten head tensors only
+        (`through`: over `outputs` too)."""
         B = outputs[0].shape[0]
-        cls, embed = self._query_side_heads_differentiable(torch.cat(outputs, dim=0))
+        cls, embed = self._query_side_heads_differentiable(torch.cat(outputs, dim=0), through)
         feat = mask_features.detach()
         return [{"pred_logits": cls[l * B:(l + 1) * B], "pred_masks": MaskLogitsFunction.apply(embed[l * B:(l + 1) * B], feat)}
                 for l in range(len(outputs))]
@@ -468,11 +653,17 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         if differentiable and isinstance(mask_features, DeferredMaskFeatures):
             # decided HERE: inside frozen() grad mode reads off.  The differentiable last call wants the map (MaskLogitsFunction), as before
             mask_features = mask_features.materialize()
-        with frozen():
-            output, mask_features, side, predictions_class, predictions_mask, head_inputs = self._decode(x, mask_features)
-        cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side)
+        through = differentiable and self.differentiable_decoder
+        if through:
+            output, mask_features, predictions_class, predictions_mask, head_inputs = self._decode_differentiable(x, mask_features)
+            cls, embed = self._query_side_heads_differentiable(output, through=True)
+            msk = MaskLogitsFunction.apply(embed, mask_features)
+        else:
+            with frozen():
+                output, mask_features, side, predictions_class, predictions_mask, head_inputs = self._decode(x, mask_features)
+            cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side)
         if differentiable and self.deep_supervision:
-            aux = self._aux_heads_differentiable(head_inputs, mask_features) if head_inputs else []
+            aux = self._aux_heads_differentiable(head_inputs, mask_features, through) if head_inputs else []
         else:
             aux = [({"pred_logits": a, "pred_masks": b} if b is not None else {"pred_logits": a})
                    for a, b in zip(predictions_class, predictions_mask)]
@@ -485,10 +676,8 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
                     out["ood_pred"] = self.ood_pred(mask_features)                   # reference :467-468
         return out
 
-    def _decode(self, x, mask_features):
-        """Everything of forward before its last head call -> (decoder-layer output [B,Q,C], contiguous mask_features, the cached query side of that
-        call (only a decoder without layers has one), class and mask predictions of the intermediate calls, the decoder-layer outputs that entered
-        those calls)."""
+    def _memory_tokens(self, x):
+        """the memory of every level as tokens: (src = x + level_embed [B,S,C], sine position embedding [B,S,C], (h, w)) per level"""
         src, pos, size_list = [], [], []
         B = x[0].shape[0]
         for i in range(self.num_feature_levels):
@@ -497,6 +686,50 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             t = x[i].permute(0, 2, 3, 1)                                                      # channels-last views (pixel decoder): tokens without a copy
             tok = t.reshape(B, -1, x[i].shape[1]) if t.is_contiguous() else x[i].flatten(2).transpose(1, 2)
             src.append(tok + self.level_embed.weight[i])                                      # [B,S,C] contiguous (:424-426)
+        return src, pos, size_list
+
+    def _decode_differentiable(self, x, mask_features):
+        """`_decode` with an autograd graph over the decoder layers (``differentiable_decoder``; see the class) -> (decoder-layer output [B,Q,C],
+        detached contiguous mask_features, class / mask predictions of the intermediate calls as in `_decode` (detached), the decoder-layer outputs
+        that entered those calls (with their graph)).  The same launches in the same order as `_decode` without the cached initial heads."""
+        B = x[0].shape[0]
+        with torch.no_grad():
+            src, pos, size_list = self._memory_tokens(x)                # frozen pixel decoder: no gradient to the memory; level_embed's own goes
+            mask_features = mask_features.detach().contiguous()         # through `level_row` below
+        train_level = self.level_embed.weight.requires_grad
+        query_embed = self.query_embed.weight[None].expand(B, -1, -1)
+        output = self.query_feat.weight[None].expand(B, -1, -1).contiguous()
+        predictions_class, predictions_mask, head_inputs = [], [], []
+        gathered = {}
+
+        def attn_mask_head(out, level):
+            with torch.no_grad():                                       # the mask is detached in the reference (:487): sparse, as in inference
+                c, m, logits = self.forward_prediction_heads(out.detach(), mask_features, size_list[level], True, need_masks=False, gathered=gathered)
+            predictions_class.append(c)
+            predictions_mask.append(m)
+            head_inputs.append(out)
+            return logits
+
+        if self.num_layers == 0:
+            return output, mask_features, predictions_class, predictions_mask, head_inputs
+        attn_logits = attn_mask_head(output, 0)
+        for i in range(self.num_layers):
+            li = i % self.num_feature_levels
+            output = self.transformer_cross_attention_layers[i].forward_differentiable(
+                output, src[li], attn_logits, pos[li], query_embed, self.level_embed.weight[li] if train_level else None)
+            output = self.transformer_self_attention_layers[i].forward_differentiable(output, query_embed)
+            output = self.transformer_ffn_layers[i].forward_differentiable(output)
+            if i == self.num_layers - 1:
+                break
+            attn_logits = attn_mask_head(output, (i + 1) % self.num_feature_levels)
+        return output, mask_features, predictions_class, predictions_mask, head_inputs
+
+    def _decode(self, x, mask_features):
+        """Everything of forward before its last head call -> (decoder-layer output [B,Q,C], contiguous mask_features, the cached query side of that
+        call (only a decoder without layers has one), class and mask predictions of the intermediate calls, the decoder-layer outputs that entered
+        those calls)."""
+        src, pos, size_list = self._memory_tokens(x)
+        B = x[0].shape[0]
         query_embed = self.query_embed.weight[None].expand(B, -1, -1)
         first = self._initial_query_side(B, mask_features.device) if self.cache_initial_heads else None
         if first is not None:

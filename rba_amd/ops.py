@@ -704,6 +704,34 @@ def masked_xattn(q, k, v, mask_logits=None, split_keys=None):
 
 
 @_hip_op
+def masked_xattn_backward(q, k, v, mask_logits, grad_out, need_q=True, need_k=True, need_v=True):
+    """K3 backward.  masked_xattn's inputs (q [B,Q,nH,hd] unscaled, k, v [B,S,nH,hd], mask_logits [B,Q,S] | None) and grad_out [B,Q,nH*hd] =
+    dL/d out -> (grad_q | None, grad_k | None, grad_v | None), the gradients of the attention core in exact fp32 (the mask gets none: the
+    reference detaches it).  A gradient that is not needed is not computed.  All three are bitwise reproducible from launch to launch."""
+    if not (need_q or need_k or need_v):
+        raise RbaHipError("masked_xattn_backward: at least one of need_q / need_k / need_v")
+    _chk(q, "q", dim=4)
+    _chk(k, "k", dim=4)
+    _chk(v, "v", dim=4)
+    B, Q, nH, hd = q.shape
+    S = k.shape[1]
+    if tuple(k.shape) != (B, S, nH, hd) or tuple(v.shape) != (B, S, nH, hd):
+        raise RbaHipError("k / v shape mismatch")
+    _shaped(mask_logits, "mask_logits", (B, Q, S), optional=True)
+    _shaped(grad_out, "grad_out", (B, Q, nH * hd))
+    dev = q.device
+    alloc = torch.empty if B and Q else torch.zeros             # no query: an empty sum, decided here
+    grad_q = torch.empty((B, Q, nH, hd), dtype=torch.float32, device=dev) if need_q else None
+    grad_k = alloc((B, S, nH, hd), dtype=torch.float32, device=dev) if need_k else None
+    grad_v = alloc((B, S, nH, hd), dtype=torch.float32, device=dev) if need_v else None
+    if B and Q:
+        ws = _scratch(_query("rba_masked_xattn_bwd_workspace_bytes", B, Q, S, nH), dev, 4)
+        _launch("rba_masked_xattn_bwd_f32", _p(q), _p(k), _p(v), _p(mask_logits), _p(grad_out), _p(grad_q), _p(grad_k), _p(grad_v), _p(ws),
+                B, Q, S, nH, hd)
+    return grad_q, grad_k, grad_v
+
+
+@_hip_op
 def mask_logits(embed, feat, mode=None):
     """K4.  einsum("bqc,bchw->bqhw") (mask2former_transformer_decoder.py:479): embed [B,Q,C], feat [B,C,h,w].  `mode` (default: _split_mode())
     "f16x3" = three f16 matrix-pipe products per fp32 product (|x| < 65504), anything else = the exact-fp32 MFMA kernel."""

@@ -6,8 +6,9 @@ trainable parameter by the reference's rules and returns a ``ClipAdamW``: full-m
 launches and, across ranks, one ``all_reduce`` per step, nothing read back.  ``WarmupPolyLR(cfg)`` is Detectron2's DeepLab schedule in closed form.
 Detectron2 is not installed where this was written: its scheduler and its SOLVER defaults are restated from its published source, parity unpinned.
 
-This library differentiates the prediction heads (``class_embed``, ``mask_embed``, ``decoder_norm``) and the ``ood_pred`` head only; a cfg that leaves
-anything else trainable is refused by name, as is every solver setting the step does not implement.  ``SOLVER.AMP`` is ignored (one logged line): the
+By default this library trains the prediction heads (``class_embed``, ``mask_embed``, ``decoder_norm``) and the ``ood_pred`` head only; a cfg that leaves
+anything else trainable is refused by name, as is every solver setting the step does not implement.  ``build_optimizer(..., differentiable_decoder=True)``
+opts in to training the transformer decoder itself (the released PEBAL recipe); backbone and pixel decoder have no backward here and stay refused.  ``SOLVER.AMP`` is ignored (one logged line): the
 fine-tune path is fp32 by design.
 """
 import logging
@@ -23,7 +24,8 @@ logger = logging.getLogger(__name__)
 # train_net.py:228-240
 NORM_MODULE_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm, nn.GroupNorm, nn.InstanceNorm1d, nn.InstanceNorm2d,
                      nn.InstanceNorm3d, nn.LayerNorm, nn.LocalResponseNorm)
-# what has a backward here: MultiScaleMaskedTransformerDecoder.differentiable_heads (+ deep_supervision) and .differentiable_ood_head
+# what has a backward here: MultiScaleMaskedTransformerDecoder.differentiable_heads (+ deep_supervision), .differentiable_ood_head and, opt-in,
+# .differentiable_decoder (every other predictor parameter)
 HEAD_MODULES = ("class_embed", "mask_embed", "decoder_norm")
 OOD_HEAD_MODULE = "ood_pred"
 PREDICTOR = "sem_seg_head.predictor."
@@ -102,31 +104,42 @@ def check_solver_settings(cfg):
     return max(float(c.CLIP_VALUE), 0.0)           # train_net.py:306-310: a value <= 0 disables the clip
 
 
-def build_optimizer(cfg, model):
+def build_optimizer(cfg, model, differentiable_decoder=False):
     """``Trainer.build_optimizer`` (train_net.py:220-333) -> ClipAdamW.  Side effects, as in the reference: ``requires_grad`` of the frozen parameters is
-    cleared; and, this library's own: the predictor's ``differentiable_heads`` / ``deep_supervision`` / ``differentiable_ood_head`` are set to what the
-    trainable set and ``MASK_FORMER.DEEP_SUPERVISION`` ask for."""
+    cleared; and, this library's own: the predictor's ``differentiable_heads`` / ``deep_supervision`` / ``differentiable_ood_head`` /
+    ``differentiable_decoder`` are set to what the trainable set and ``MASK_FORMER.DEEP_SUPERVISION`` ask for.
+
+    ``differentiable_decoder`` (opt-in; ``train_net --differentiable_decoder``): any trainable subset of ``sem_seg_head.predictor.*`` is accepted --
+    the released PEBAL recipe (FREEZE_BACKBONE + FREEZE_PIXEL_DECODER: the whole transformer decoder) and
+    FREEZE_TRANSFORMER_DECODER_EXCEPT_OBJECT_QUERIES -- and the predictor's ``differentiable_decoder`` is set iff a trainable parameter lies outside
+    the heads and ``ood_pred``.  A trainable backbone or pixel-decoder parameter is refused either way."""
     max_norm = check_solver_settings(cfg)
     if cfg.SOLVER.get("AMP", {}).get("ENABLED", False):
         logger.info("SOLVER.AMP.ENABLED is ignored: the fine-tune path of this library is fp32 by design")
     apply_freeze_flags(cfg, model)
     groups = param_groups(cfg, model)
-    heads = ood = False
+    heads = ood = layers = False
     for name, _, _, _ in groups:
         part = name[len(PREDICTOR):].split(".")[0] if name.startswith(PREDICTOR) else None
         if part in HEAD_MODULES:
             heads = True
         elif part == OOD_HEAD_MODULE:
             ood = True
+        elif part is not None and differentiable_decoder:
+            layers = True
         else:
             raise ValueError(f"{name} would be trained, but this library has backward kernels for the prediction heads ({', '.join(HEAD_MODULES)}) and "
-                             f"the {OOD_HEAD_MODULE} head only: set {_flag_that_would_freeze(name)}: True (the COCO-mix and DenseHybrid recipes set such flags)")
+                             f"the {OOD_HEAD_MODULE} head only: set {_flag_that_would_freeze(name)}: True (the COCO-mix and DenseHybrid recipes set such flags)"
+                             + ("" if part is None or differentiable_decoder else
+                                "; or train the transformer decoder itself with build_optimizer(..., differentiable_decoder=True) / "
+                                "train_net --differentiable_decoder"))
     if not groups:
         raise ValueError("the MODEL.FREEZE_* flags leave no trainable parameter")
     predictor = model.sem_seg_head.predictor
     predictor.differentiable_heads = True          # the ood head's graph hangs off the differentiable head call too
-    predictor.deep_supervision = bool(heads and cfg.MODEL.MASK_FORMER.get("DEEP_SUPERVISION", True))
+    predictor.deep_supervision = bool((heads or layers) and cfg.MODEL.MASK_FORMER.get("DEEP_SUPERVISION", True))
     predictor.differentiable_ood_head = ood
+    predictor.differentiable_decoder = layers
     return ClipAdamW([(n, p) for n, p, _, _ in groups], [m for _, _, m, _ in groups], [w for _, _, _, w in groups], max_norm=max_norm)
 
 

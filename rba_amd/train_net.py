@@ -207,6 +207,9 @@ def build_parser():
                                                      "$DETECTRON2_DATASETS/INPUT.COCO_ROOT)")
     p.add_argument("--output_dir", default=None, help="default: the cfg's OUTPUT_DIR, else ./output")
     p.add_argument("--resume", action="store_true")
+    p.add_argument("--differentiable_decoder", action="store_true",
+                   help="train whatever the cfg leaves trainable inside the transformer decoder (the released PEBAL recipe: all of it; "
+                        "FREEZE_TRANSFORMER_DECODER_EXCEPT_OBJECT_QUERIES: the queries); without it such a cfg is refused")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--num_workers", type=int, default=8, help="image-decoding threads (at most 16)")
     p.add_argument("--log_period", type=int, default=20)
@@ -242,7 +245,7 @@ def main(argv=None):
         logger.info("MODEL.WEIGHTS %r not found: training from the model's initial weights", weights)
     model.to(device)
     model.graph_replay = False
-    optimizer = build_optimizer(cfg, model)                      # after .to(device): the step holds the parameters' device pointers
+    optimizer = build_optimizer(cfg, model, differentiable_decoder=args.differentiable_decoder)      # after .to(device): the step holds the parameters' device pointers
     scheduler, criterion = WarmupPolyLR(cfg), criterion_for_recipe(cfg)
     trainer = Trainer(cfg, model, criterion, None, optimizer, scheduler, output_dir, log_period=args.log_period)
     start = trainer.resume() if args.resume else 0
