@@ -22,6 +22,7 @@ constexpr int K15_MAX_PARTIALS = 1024;                 // RBA_ADAMW_MAX_PARTIALS
 static_assert(K15_MAX_PARTIALS == RBA_ADAMW_MAX_PARTIALS && K15_MAX_PARTIALS == 4 * K15_THREADS, "K15b reads at most four partials per thread");
 
 // the workgroup's sum, the same bits in every thread: xor-shuffle tree per wave, then the waves' slots in index order
+// (not loss_reduce.h's loss_block_reduce: ((s0 + s1) + s2) + s3 is another order than its (s0 + s1) + (s2 + s3), and the order is the bits)
 __device__ __forceinline__ float block_sum(float v, float* slots /* [K15_WAVES] LDS */) {
   v = wave_reduce_sum(v);
   if ((threadIdx.x & (RBA_WAVE - 1)) == 0) slots[threadIdx.x / RBA_WAVE] = v;

@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "masked_xattn_bwd.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip", "pebal_loss.hip", "tta_merge.hip", "resize_u8.hip", "confusion.hip", "train_view.hip", "adamw_step.hip",
            "swin_window_attn.hip", "swin_attn_block.hip", "group_norm.hip", "layer_norm.hip", "skinny_linear.hip", "split_linear.hip", "split_linear_dma.hip", "split_linear_gnf.hip", "gaussian_blur.hip", "open_panoptic.hip", "dense_hybrid.hip", "patch_embed.hip", "token_linear.hip", "decoder_small.hip"]
-HEADERS = ["common.h", "knobs.h", "bilinear_ac.h", "rba_reduce_kernels.h", "split_linear_dma.h", "split_linear_h3.h", "split_linear_h3q.h", "mlp_fused_h3.h", "swin_window_attn_h3.h", "swin_attn_block.h",
+HEADERS = ["common.h", "knobs.h", "bilinear_ac.h", "loss_reduce.h", "gaussian_blur.h", "rba_reduce_kernels.h", "split_linear_dma.h", "split_linear_h3.h", "split_linear_h3q.h", "mlp_fused_h3.h", "swin_window_attn_h3.h", "swin_attn_block.h",
            os.path.join("..", "..", "include", "rba_hip.h")]
 TUNE_SOURCES = [os.path.join("tune", "rba_reduce_tune.hip"), os.path.join("tune", "split_linear_tune.hip"), os.path.join("tune", "split_linear_ws.hip"), os.path.join("tune", "mlp_fused_h1.hip"), os.path.join("tune", "k5_timing.hip"), os.path.join("tune", "k5_wpe_ab.hip"), os.path.join("tune", "k5_wpe_plain.hip"), os.path.join("tune", "k5_persist.hip"), os.path.join("tune", "k7_timing.hip")] + [os.path.join("tune", f"gnf_form{f}_dbg{d}.hip") for f in (0, 1) for d in (0, 1)] + [os.path.join("tune", "gnf_form0_dbg1_unpacked.hip"), os.path.join("tune", "gnf_form1_dbg0_unpacked.hip")]
 TUNE_LIB = os.path.join(HERE, "tune", "librba_tune.so")

@@ -106,6 +106,11 @@ __device__ __forceinline__ float wave_reduce_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, RBA_WAVE);
   return v;
 }
+__device__ __forceinline__ int wave_reduce_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, RBA_WAVE);
+  return v;
+}
 
 // Source coordinate of ATen's upsample_bilinear2d (align_corners=False): scale*(dst+0.5)-0.5 clamped at 0.
 struct BilinearTap {

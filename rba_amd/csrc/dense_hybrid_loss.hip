@@ -3,68 +3,37 @@
 // the channels, get_batch_avg's global mean, the two nll_loss means -- and all of it backward.  The upsampled maps never exist: every label pixel
 // samples its K + 2 values out of the quarter-resolution maps.  fp32, wave64, no MFMA, no scratch.  docs/kernels/K10.md.
 //
-// Per label pixel P (taps and weights: bilinear_ac.h, K9's):  x_k = sample of sem[b,k], o_c = sample of ood[b,c], L = logsumexp_k x_k.
+// Per label pixel P (taps and weights: bilinear_ac.h):  x_k = sample of sem[b,k], o_c = sample of ood[b,c], L = logsumexp_k x_k.
 //   label < K: class;  254: outlier;  anything else: ignored by the segmentation term (the reference maps 254 and 255 to ignore_index)
 //   S_seg = sum_{label<K} (L - x_label), n_seg      S_ood = sum_{label=254} L, n_ood
 //   S_th  = sum_all (logsumexp_c o_c - o_[label=254])   (void pixels are target 0, as in the reference)      S_x = sum_all sum_k x_k
 //   m = S_x / (B K H W)  (get_batch_avg: detached)   loss_seg = S_seg / n_seg   loss_ood = S_ood / n_ood - m   loss_th = S_th / (B H W)
 //   loss = loss_seg + beta loss_ood + 10 beta loss_th                       n_seg == 0 or n_ood == 0: NaN, the mean of nothing, as in the reference
 //
-// (a) dh_partial_kernel: K9's walk -- a workgroup takes pixels wg 256 + tid + j G 256 in ascending order, a fixed shuffle / LDS tree, its four
-//     sums and two integer counts to the caller's workspace with plain stores; L goes to the [B,H,W] map `lse` for the backward.
-//     dh_finish_kernel = one workgroup that adds the partials in a fixed order and forms losses [4] and stats [8] on the device.
-// (b) dh_bwd_kernel, gather form: 16 lanes own one quarter-resolution pixel (b, y, x) of all K + 2 channels.  They find the label rows / columns
-//     whose taps name it (a contiguous range: the first tap index never decreases along an axis), split that rectangle among themselves (lane s
-//     takes candidates s, s + 16, ... in ascending order), recompute each candidate's samples with the forward's functions, p_k = exp(x_k - L)
-//     from the saved L, and add weight * d loss / d x_k; a fixed xor tree over the 16 lanes, plain stores.  A pixel nobody samples gets 0.
+// (a) dh_partial_kernel + dh_finish_kernel: the partial / finish scheme of loss_reduce.h, four sums and two counts, one pixel to a thread before the
+//     cap; L goes to the [B,H,W] map `lse` for the backward.  The finish forms losses [4] and stats [8] on the device.
+// (b) dh_bwd_kernel, gather form: the 16-lane walk of bilinear_ac.h (AcOwner) -- 16 lanes own one quarter-resolution pixel (b, y, x) of all K + 2
+//     channels and split the rectangle of label pixels whose taps name it.  For each candidate they recompute its samples with the forward's
+//     functions, p_k = exp(x_k - L) from the saved L, and add weight * d loss / d x_k; ac_split_sum, plain stores.  A pixel nobody samples gets 0.
 #include "bilinear_ac.h"
+#include "loss_reduce.h"
 #include "../../include/rba_hip.h"
 
 namespace {
 
-constexpr int DH_THREADS = 256, DH_MAX_GROUPS = 2048, DH_WS = 8;    // workspace words per workgroup: S_seg S_ood S_th S_x n_seg n_ood - -
-constexpr int DH_SPLIT = 16, DH_OWNERS = DH_THREADS / DH_SPLIT;     // backward: lanes per owner pixel, owner pixels per workgroup
+constexpr int DH_THREADS = LOSS_THREADS, DH_WS = 8;                 // workspace words per workgroup: S_seg S_ood S_th S_x n_seg n_ood - -
+constexpr int DH_OWNERS = DH_THREADS / AC_SPLIT;                    // backward: owner pixels per workgroup
 constexpr int DH_OUTLIER = 254;
-
-int dh_groups(int64_t total) {
-  const int64_t g = (total + DH_THREADS - 1) / DH_THREADS;
-  return (int)(g < DH_MAX_GROUPS ? g : DH_MAX_GROUPS);
-}
-
-// four float sums and two integer counts of a workgroup's 256 threads -> thread 0 .. 5 hold one each (returned in `out`, valid for tid < 6)
-__device__ __forceinline__ float dh_block_reduce(float s0, float s1, float s2, float s3, int n0, int n1, float (*red)[6]) {
-  const int tid = threadIdx.x;
-  s0 = wave_reduce_sum(s0);
-  s1 = wave_reduce_sum(s1);
-  s2 = wave_reduce_sum(s2);
-  s3 = wave_reduce_sum(s3);
-  n0 = wave_reduce_sum_int(n0);
-  n1 = wave_reduce_sum_int(n1);
-  if ((tid & 63) == 0) {
-    float* r = red[tid >> 6];
-    r[0] = s0, r[1] = s1, r[2] = s2, r[3] = s3;
-    r[4] = __int_as_float(n0), r[5] = __int_as_float(n1);
-  }
-  __syncthreads();
-  float out = 0.f;
-  if (tid < 4) out = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-  else if (tid < 6)
-    out = __int_as_float((__float_as_int(red[0][tid]) + __float_as_int(red[1][tid])) + (__float_as_int(red[2][tid]) + __float_as_int(red[3][tid])));
-  return out;
-}
 
 template <int KMAX, int LB>
 __global__ __launch_bounds__(DH_THREADS) void dh_partial_kernel(const float* __restrict__ sem, const float* __restrict__ ood,
                                                                 const void* __restrict__ labels, int K, int h, int w, int H, int W, int64_t total,
                                                                 float* __restrict__ ws, float* __restrict__ lse) {
-  __shared__ float red[DH_THREADS / 64][6];
-  const int tid = threadIdx.x;
   const float sy = ac_scale(h, H), sx = ac_scale(w, W);
   const int hw = h * w;
   const uint32_t HW = (uint32_t)H * W, stride = gridDim.x * DH_THREADS, end = (uint32_t)total;    // B H W < 2^31: i + stride stays below 2^32
-  float s_seg = 0.f, s_ood = 0.f, s_th = 0.f, s_x = 0.f;
-  int n_seg = 0, n_ood = 0;
-  for (uint32_t i = blockIdx.x * DH_THREADS + tid; i < end; i += stride) {
+  LossSums<4, 2> a{};                                     // f: S_seg, S_ood, S_th, S_x; n: n_seg, n_ood
+  for (uint32_t i = blockIdx.x * DH_THREADS + threadIdx.x; i < end; i += stride) {
     const int lab = ac_label<LB>(labels, i);
     const int b = (int)(i / HW), r = (int)(i - (uint32_t)b * HW), Y = r / W, X = r - Y * W;
     const AcTaps4 t = ac_taps4(tap_of(Y, sy, h), tap_of(X, sx, w), w);
@@ -87,45 +56,26 @@ __global__ __launch_bounds__(DH_THREADS) void dh_partial_kernel(const float* __r
       if (k < K) e += expf(x[k] - mx);
     const float L = mx + logf(e);
     lse[i] = L;
-    s_x += sum_x;
+    a.f[3] += sum_x;
     if (lab < K) {
-      s_seg += L - x_lab;
-      ++n_seg;
+      a.f[0] += L - x_lab;
+      ++a.n[0];
     } else if (lab == DH_OUTLIER) {
-      s_ood += L;
-      ++n_ood;
+      a.f[1] += L;
+      ++a.n[1];
     }
     const float* op = ood + (int64_t)b * 2 * hw;
     const float o0 = ac_sample(op, t), o1 = ac_sample(op + hw, t), om = fmaxf(o0, o1);
-    s_th += om + logf(expf(o0 - om) + expf(o1 - om)) - (lab == DH_OUTLIER ? o1 : o0);
+    a.f[2] += om + logf(expf(o0 - om) + expf(o1 - om)) - (lab == DH_OUTLIER ? o1 : o0);
   }
-  const float v = dh_block_reduce(s_seg, s_ood, s_th, s_x, n_seg, n_ood, red);
-  if (tid < 6) ws[DH_WS * (int64_t)blockIdx.x + tid] = v;
+  loss_store_partial<DH_WS>(a, ws);
 }
 
-// thread t takes the partials t, t + 256, ... in ascending order, then the same fixed tree
 __global__ __launch_bounds__(DH_THREADS) void dh_finish_kernel(const float* __restrict__ ws, int G, int64_t total, int K, float beta,
                                                                float* __restrict__ losses, float* __restrict__ stats) {
-  __shared__ float red[DH_THREADS / 64][6];
-  __shared__ float fin[6];
-  const int tid = threadIdx.x;
-  float s_seg = 0.f, s_ood = 0.f, s_th = 0.f, s_x = 0.f;
-  int n_seg = 0, n_ood = 0;
-  for (int g = tid; g < G; g += DH_THREADS) {
-    const float* p = ws + DH_WS * (int64_t)g;
-    s_seg += p[0];
-    s_ood += p[1];
-    s_th += p[2];
-    s_x += p[3];
-    n_seg += __float_as_int(p[4]);
-    n_ood += __float_as_int(p[5]);
-  }
-  const float v = dh_block_reduce(s_seg, s_ood, s_th, s_x, n_seg, n_ood, red);
-  if (tid < 6) fin[tid] = v;
-  __syncthreads();
-  if (tid == 0) {
-    const float S_seg = fin[0], S_ood = fin[1], S_th = fin[2], S_x = fin[3];
-    const float N_seg = (float)__float_as_int(fin[4]), N_ood = (float)__float_as_int(fin[5]), N = (float)total;
+  loss_finish<DH_WS, 4, 2>(ws, G, [=](const LossSums<4, 2>& t) {
+    const float S_seg = t.f[0], S_ood = t.f[1], S_th = t.f[2], S_x = t.f[3];
+    const float N_seg = (float)t.n[0], N_ood = (float)t.n[1], N = (float)total;
     const float m = S_x / (N * (float)K);
     const float loss_seg = S_seg / N_seg;                 // 0 / 0 = NaN, the mean of nothing
     const float loss_ood = S_ood / N_ood - m;
@@ -136,7 +86,7 @@ __global__ __launch_bounds__(DH_THREADS) void dh_finish_kernel(const float* __re
     losses[3] = loss_th;
     stats[0] = S_seg, stats[1] = S_ood, stats[2] = S_th, stats[3] = S_x;
     stats[4] = N_seg, stats[5] = N_ood, stats[6] = N, stats[7] = m;
-  }
+  });
 }
 
 template <int KMAX, int LB>
@@ -145,60 +95,42 @@ __global__ __launch_bounds__(DH_THREADS) void dh_bwd_kernel(const float* __restr
                                                             int W, int64_t pixels, float beta, const float* __restrict__ stats,
                                                             const float* __restrict__ grad_loss, float* __restrict__ grad_sem,
                                                             float* __restrict__ grad_ood) {
-  const int sub = threadIdx.x & (DH_SPLIT - 1);
-  const int64_t owner = (int64_t)blockIdx.x * DH_OWNERS + (threadIdx.x >> 4);
-  const bool live = owner < pixels;
-  const int64_t i = live ? owner : pixels - 1;            // a group past the end walks nothing and stores nothing, but takes part in the shuffles
-  const int hw = h * w, b = (int)(i / hw), r = (int)(i - (int64_t)b * hw), y = r / w, x = r - y * w;
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
+  const AcOwner o = ac_owner(DH_OWNERS, pixels, h, w, H, W);
+  const int hw = h * w;
   const float g = *grad_loss;
   // d loss / d (a pixel's term): the means' 1 / n
   const float c_seg = g / stats[4], c_ood = g * beta / stats[5], c_th = g * 10.0f * beta / stats[6];
-  int Y0, Y1, X0, X1;
-  ac_naming(y, sy, h, H, Y0, Y1);
-  ac_naming(x, sx, w, W, X0, X1);
-  const uint32_t nX = X1 >= X0 ? X1 - X0 + 1 : 0;
-  const uint32_t n = live && Y1 >= Y0 ? (uint32_t)(Y1 - Y0 + 1) * nX : 0;      // <= H W < 2^31: c + 16 stays below 2^32
-  const float* sp = sem + (int64_t)b * K * hw;
-  const float* op = ood + (int64_t)b * 2 * hw;
+  const float* sp = sem + (int64_t)o.b * K * hw;
+  const float* op = ood + (int64_t)o.b * 2 * hw;
   float acc[KMAX], a0 = 0.f, a1 = 0.f;
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) acc[k] = 0.f;
-  for (uint32_t c = sub; c < n; c += DH_SPLIT) {
-    const uint32_t dy = c / nX;
-    const int Y = Y0 + (int)dy, X = X0 + (int)(c - dy * nX);
-    const AcTap ty = tap_of(Y, sy, h), tx = tap_of(X, sx, w);
-    const float wgt = tap_weight(ty, y) * tap_weight(tx, x);
-    const AcTaps4 t = ac_taps4(ty, tx, w);
-    const int64_t P = ((int64_t)b * H + Y) * W + X;
-    const int lab = ac_label<LB>(labels, P);
+  for (uint32_t c = o.sub; c < o.n; c += AC_SPLIT) {
+    const AcCandidate q = ac_candidate(o, c);
+    const int lab = ac_label<LB>(labels, q.P);
     const bool out = lab == DH_OUTLIER;
-    const float o0 = ac_sample(op, t), o1 = ac_sample(op + hw, t), om = fmaxf(o0, o1);
+    const float o0 = ac_sample(op, q.t), o1 = ac_sample(op + hw, q.t), om = fmaxf(o0, o1);
     const float e0 = expf(o0 - om), e1 = expf(o1 - om), es = e0 + e1;
-    a0 = fmaf(wgt, e0 / es - (out ? 0.f : 1.0f), a0);
-    a1 = fmaf(wgt, e1 / es - (out ? 1.0f : 0.f), a1);
+    a0 = fmaf(q.wgt, e0 / es - (out ? 0.f : 1.0f), a0);
+    a1 = fmaf(q.wgt, e1 / es - (out ? 1.0f : 0.f), a1);
     if (lab < K || out) {
-      const float cw = wgt * (out ? c_ood : c_seg), L = lse[P];
+      const float cw = q.wgt * (out ? c_ood : c_seg), L = lse[q.P];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k)
-        if (k < K) acc[k] = fmaf(cw, expf(ac_sample(sp + (int64_t)k * hw, t) - L) - (k == lab ? 1.0f : 0.f), acc[k]);
+        if (k < K) acc[k] = fmaf(cw, expf(ac_sample(sp + (int64_t)k * hw, q.t) - L) - (k == lab ? 1.0f : 0.f), acc[k]);
     }
   }
-  // the 16 lanes of an owner, a fixed xor tree (every lane of the wave is here)
+  a0 = ac_split_sum(a0);
+  a1 = ac_split_sum(a1);
 #pragma unroll
-  for (int o = DH_SPLIT / 2; o > 0; o >>= 1) {
-    a0 += __shfl_xor(a0, o, RBA_WAVE);
-    a1 += __shfl_xor(a1, o, RBA_WAVE);
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) acc[k] += __shfl_xor(acc[k], o, RBA_WAVE);
-  }
-  if (live && sub == 0) {
-    float* gs = grad_sem + (int64_t)b * K * hw + r;
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) acc[k] = ac_split_sum(acc[k]);
+  if (o.live && o.sub == 0) {
+    float* gs = grad_sem + (int64_t)o.b * K * hw + o.r;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < K) gs[(int64_t)k * hw] = acc[k];
-    float* go = grad_ood + (int64_t)b * 2 * hw + r;
+    float* go = grad_ood + (int64_t)o.b * 2 * hw + o.r;
     go[0] = c_th * a0;
     go[hw] = c_th * a1;
   }
@@ -213,7 +145,7 @@ bool dh_shape_ok(int B, int K, int h, int w, int H, int W) {
 
 extern "C" int rba_dense_hybrid_loss_workspace_f32(int B, int H, int W, int64_t* bytes) {
   RBA_CHECK_ARG(bytes && B >= 1 && H >= 1 && W >= 1 && (int64_t)B * H * W <= 0x7fffffffLL && (int64_t)H * W <= 0x7fffffffLL);
-  *bytes = (int64_t)dh_groups((int64_t)B * H * W) * DH_WS * (int64_t)sizeof(float);
+  *bytes = (int64_t)loss_groups((int64_t)B * H * W, 1) * DH_WS * (int64_t)sizeof(float);
   return 0;
 }
 
@@ -236,7 +168,7 @@ extern "C" int rba_dense_hybrid_loss_fwd_f32(const float* sem, const float* ood,
   rba_begin();
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)B * H * W;
-  const int G = dh_groups(total);
+  const int G = loss_groups(total, 1);
 #define DH_PARTIAL(KM, LB) \
   hipLaunchKernelGGL((dh_partial_kernel<KM, LB>), dim3(G), dim3(DH_THREADS), 0, st, sem, ood, labels, K, h, w, H, W, total, workspace, lse)
   DH_DISPATCH(DH_PARTIAL);

@@ -10,7 +10,7 @@
 // (a) point_sample_kernel: one thread per (row, point), the row's plane through an optional index vector.
 // (b) the loss: loss_sums_kernel = one workgroup of 1024 threads per matched mask, every thread a fixed set of points, a fixed shuffle / LDS tree:
 //     the four sums of a mask (bce, sigma t, sigma, t) are bitwise reproducible; loss_finish_kernel = one workgroup that forms both scalar losses
-//     from them in a fixed order.  loss_bwd_kernel = one thread per (mask, point): it recomputes x and sigma, forms d loss / d x from the saved
+//     from them in a fixed order (the workgroup tree of loss_reduce.h).  loss_bwd_kernel = one thread per (mask, point): it recomputes x and sigma, forms d loss / d x from the saved
 //     sums and the two upstream gradients (device pointers) and adds its four tap contributions into the zero-filled gradient tensor with float
 //     atomics.  Sizing (the recipe: 2 images x ~20 targets, P = 12544): 38 x 12544 x 4 taps x 4 B = 7.6 MB of added bytes as scattered single
 //     dwords against a chip-wide rate of ~1.3 TB/s for WELL-SHAPED float atomics -- a floor of 6 us that scattered dwords will not reach -- beside
@@ -24,6 +24,7 @@
 //     known value.  Neither [Q,P] nor [T,P] goes to memory.
 #include <math.h>
 #include "common.h"
+#include "loss_reduce.h"
 #include "../../include/rba_hip.h"
 
 namespace {
@@ -93,7 +94,7 @@ constexpr int LS_THREADS = 1024;
 __global__ __launch_bounds__(LS_THREADS) void loss_sums_kernel(const float* __restrict__ masks, const int64_t* __restrict__ index,
                                                                const float* __restrict__ coords, const float* __restrict__ labels,
                                                                float* __restrict__ sums, int64_t num_planes, int h, int w, int P) {
-  __shared__ float red[LS_THREADS / 64][4];
+  __shared__ float red[LS_THREADS / 64][4];                 // (not loss_reduce.h's tree: 1024 threads, and the 16 waves are added in index order)
   const int n = blockIdx.x, tid = threadIdx.x;
   const int64_t pl = plane_of(index, n, num_planes);
   float s[4] = {0.f, 0.f, 0.f, 0.f};
@@ -126,24 +127,18 @@ __global__ __launch_bounds__(LS_THREADS) void loss_sums_kernel(const float* __re
 }
 
 // losses[0] = sum_n (bce_n / P) / num_masks, losses[1] = sum_n [1 - (2 a + 1) / (b + c + 1)] / num_masks: thread t takes masks t, t + 256, ...
-// in ascending order, then a fixed tree
-__global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restrict__ sums, float* __restrict__ losses, int N, int P, float num_masks) {
-  __shared__ float red[4][2];
+// in ascending order, then loss_reduce.h's tree
+__global__ __launch_bounds__(LOSS_THREADS) void loss_finish_kernel(const float* __restrict__ sums, float* __restrict__ losses, int N, int P,
+                                                                   float num_masks) {
   const int tid = threadIdx.x;
-  float lm = 0.f, ld = 0.f;
-  for (int n = tid; n < N; n += 256) {
+  LossSums<2, 0> a{};                                       // f: the masks' bce means, their dice terms
+  for (int n = tid; n < N; n += LOSS_THREADS) {
     const float* s = sums + 4 * (int64_t)n;
-    lm += s[0] / (float)P;
-    ld += 1.0f - (2.0f * s[1] + 1.0f) / (s[2] + s[3] + 1.0f);
+    a.f[0] += s[0] / (float)P;
+    a.f[1] += 1.0f - (2.0f * s[1] + 1.0f) / (s[2] + s[3] + 1.0f);
   }
-  lm = wave_reduce_sum(lm);
-  ld = wave_reduce_sum(ld);
-  if ((tid & 63) == 0) {
-    red[tid >> 6][0] = lm;
-    red[tid >> 6][1] = ld;
-  }
-  __syncthreads();
-  if (tid < 2) losses[tid] = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) / num_masks;
+  const float v = loss_block_reduce(a);
+  if (tid < 2) losses[tid] = v / num_masks;
 }
 
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ masks, const int64_t* __restrict__ index,
@@ -302,7 +297,7 @@ extern "C" int rba_mask_point_loss_fwd_f32(const float* pred_masks, const int64_
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(loss_sums_kernel, dim3(N), dim3(LS_THREADS), 0, st, pred_masks, plane_index, coords, labels, sums, num_planes, h, w, P);
   if (const int e = rba_launch_status()) return e;
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, sums, losses, N, P, num_masks);
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(LOSS_THREADS), 0, st, sums, losses, N, P, num_masks);
   return rba_launch_status();
 }
 

@@ -108,6 +108,19 @@ def _shaped(t, name, shape, optional=False):
     return t
 
 
+def _one_element(t, name):
+    """An upstream gradient of a scalar loss: a one-element fp32 device tensor (the kernels read it on the device)."""
+    if _chk(t, name).numel() != 1:
+        raise RbaHipError(f"{name} must have one element, got shape {tuple(t.shape)}")
+    return t
+
+
+def _labels(labels, name="labels"):
+    """The label map of the loss kernels K9 - K11: int64 or uint8, contiguous, [B,H,W] -> bytes per label (what the entry points' `label_bytes` takes)."""
+    _chk(labels, name, dtype=torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64, dim=3)
+    return labels.element_size()
+
+
 def _packed(planes, K, out_features=None, bf16x6=True):
     """The layout contract of split_weight's output for a weight [N, K]: [ceil(N / 128), K / 16, P, 128, 2, 8] with P = 2 float16 planes (the f16x3 form) or,
     where the wrapper has a bf16x6 kernel, P = 3 bfloat16 planes -- the dtype says which.  N = ``out_features``, or all packed rows.  -> (N, f16)."""
@@ -164,16 +177,16 @@ def _mode(score):
     return SCORE_MODES[score]
 
 
-_K1_WORKSPACES = {}       # (device, stream, "tiles" | "grad_prob" | "grad_embed") -> buffer
+_STREAM_WORKSPACES = {}   # (device, stream, kind) -> buffer: "tiles" (K1's counter) and one kind per kernel with partial sums
 
 
 def _stream_workspace(kind, device, words, alloc, dtype):
     """The per-(device, stream) buffers: one of each kind per stream that launches, replaced by a larger one when a call needs more.  Launches that
     share a buffer are ordered by their stream, and torch's allocator keeps a replaced buffer's memory on that stream."""
     key = (device.index, _stream(), kind)                # called under _hip_op: the current device IS `device`
-    ws = _K1_WORKSPACES.get(key)
+    ws = _STREAM_WORKSPACES.get(key)
     if ws is None or ws.numel() < words:
-        ws = _K1_WORKSPACES[key] = alloc(words, dtype=dtype, device=device)
+        ws = _STREAM_WORKSPACES[key] = alloc(words, dtype=dtype, device=device)
     return ws
 
 
@@ -182,10 +195,13 @@ def _k1_workspace(device):
     return _stream_workspace("tiles", device, 2, torch.zeros, torch.int32)
 
 
-def _k1_bwd_workspace(device, nbytes):
-    """K1 backward's per-tile grad_prob partial sums: grow-only (a run over varying mask sizes keeps the largest, not one per size); the kernel writes
-    every word it later reads."""
-    return _stream_workspace("grad_prob", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+def _workspace(query_name, kind, device, *dims):
+    """A kernel's partial sums (K1 / K4 backward, match_cost, the loss kernels K9 - K11): the library's `query_name(*dims, &bytes)` says how many bytes
+    this call needs -> (the stream's `kind` buffer of at least that size, the bytes).  Grow-only (a run over varying sizes keeps the largest, not one
+    per size); every such kernel writes each word it later reads."""
+    n = ctypes.c_int64(0)
+    _lib.check(_query(query_name, *dims, ctypes.addressof(n)), query_name)
+    return _stream_workspace(kind, device, max(int(n.value) // 4, 1), torch.empty, torch.float32), int(n.value)
 
 
 @_hip_op
@@ -238,12 +254,7 @@ def _k1_backward_args(who, mask_pred, cls_prob, grad, grad_name, grad_shape, nee
     if not (need_mask or need_prob):
         raise RbaHipError(f"{who}: at least one of need_mask / need_prob")
     dev = mask_pred.device
-    ws, ws_bytes = None, 0
-    if need_prob:
-        n = ctypes.c_int64(0)
-        _lib.check(_query("rba_reduce_bwd_workspace_f32", Q, K, H * W, ctypes.addressof(n)), "rba_reduce_bwd_workspace_f32")
-        ws_bytes = int(n.value)
-        ws = _k1_bwd_workspace(dev, ws_bytes)
+    ws, ws_bytes = _workspace("rba_reduce_bwd_workspace_f32", "grad_prob", dev, Q, K, H * W) if need_prob else (None, 0)
     grad_mask = torch.empty((Q, H, W), dtype=torch.float32, device=dev) if need_mask else None
     grad_prob = torch.empty((Q, K), dtype=torch.float32, device=dev) if need_prob else None
     return Q, K, H * W, ws, ws_bytes, grad_mask, grad_prob
@@ -749,11 +760,6 @@ def mask_logits(embed, feat, mode=None):
     return out
 
 
-def _k4_bwd_workspace(device, nbytes):
-    """K4 backward's per-slice grad_embed partial sums: per (device, stream) and grow-only like K1 backward's; the kernel writes every word it later reads."""
-    return _stream_workspace("grad_embed", device, max(nbytes // 4, 1), torch.empty, torch.float32)
-
-
 @_hip_op
 def mask_logits_backward(embed, feat, grad_out, need_embed=True, need_feat=True):
     """K4 backward.  embed [B,Q,C], feat [B,C,N] or [B,C,h,w] (mask_logits' inputs), grad_out [B,Q] + feat.shape[2:] = dL/d out ->
@@ -776,12 +782,7 @@ def mask_logits_backward(embed, feat, grad_out, need_embed=True, need_feat=True)
     _shaped(feat, "feat", (B, C) + sp, optional=True)
     N = math.prod(sp)
     dev = grad_out.device
-    ws, ws_bytes = None, 0
-    if need_embed:
-        n = ctypes.c_int64(0)
-        _lib.check(_query("rba_mask_logits_bwd_workspace_f32", B, Q, C, N, ctypes.addressof(n)), "rba_mask_logits_bwd_workspace_f32")
-        ws_bytes = int(n.value)
-        ws = _k4_bwd_workspace(dev, ws_bytes)
+    ws, ws_bytes = _workspace("rba_mask_logits_bwd_workspace_f32", "grad_embed", dev, B, Q, C, N) if need_embed else (None, 0)
     alloc = torch.empty if B and Q and N else torch.zeros          # an empty reduction: the entry point is a no-op, the gradient is 0
     grad_embed = alloc((B, Q, C), dtype=torch.float32, device=dev) if need_embed else None
     grad_feat = alloc((B, C) + sp, dtype=torch.float32, device=dev) if need_feat else None
@@ -871,17 +872,12 @@ def mask_point_loss_backward(pred_masks, plane_index, point_coords, point_labels
     if grad_loss_mask is None and grad_loss_dice is None:
         raise RbaHipError("mask_point_loss_backward: at least one of grad_loss_mask / grad_loss_dice")
     for g, name in ((grad_loss_mask, "grad_loss_mask"), (grad_loss_dice, "grad_loss_dice")):
-        if g is not None and _chk(g, name).numel() != 1:
-            raise RbaHipError(f"{name} must have one element, got shape {tuple(g.shape)}")
+        if g is not None:
+            _one_element(g, name)
     grad = torch.empty(pred_masks.shape, dtype=torch.float32, device=pred_masks.device)
     _launch("rba_mask_point_loss_bwd_f32", _p(pred_masks), _p(plane_index), _p(point_coords), _p(point_labels), _p(sums), _p(grad_loss_mask),
             _p(grad_loss_dice), _p(grad), M, N, h, w, P, float(num_masks))
     return grad
-
-
-def _match_cost_workspace(device, nbytes):
-    """match_cost's per-slice partial sums: per (device, stream) and grow-only like K1 / K4 backward's; the kernel writes every word it later reads."""
-    return _stream_workspace("match_cost", device, max(nbytes // 4, 1), torch.empty, torch.float32)
 
 
 @_hip_op
@@ -904,12 +900,10 @@ def match_cost(pred_masks, tgt_masks, coords, cls_prob, tgt_ids, cost_mask=1.0, 
     if bool(((tgt_ids < 0) | (tgt_ids >= K1)).any()):
         raise RbaHipError(f"match_cost: tgt_ids must lie in [0, {K1 - 1}]")
     dev = pred_masks.device
-    n = ctypes.c_int64(0)
-    _lib.check(_query("rba_match_cost_workspace_f32", Q, T, P, ctypes.addressof(n)), "rba_match_cost_workspace_f32")
-    ws = _match_cost_workspace(dev, int(n.value))
+    ws, ws_bytes = _workspace("rba_match_cost_workspace_f32", "match_cost", dev, Q, T, P)
     cost = torch.empty((Q, T), dtype=torch.float32, device=dev)
     _launch("rba_match_cost_f32", _p(pred_masks), _p(tgt_masks), _p(coords), _p(cls_prob), _p(tgt_ids), _p(cost), Q, T, P, h, w, H, W, K1,
-            float(cost_mask), float(cost_class), float(cost_dice), _p(ws), int(n.value))
+            float(cost_mask), float(cost_class), float(cost_dice), _p(ws), ws_bytes)
     return cost
 
 
@@ -920,19 +914,14 @@ def _outlier_tail_args(score, labels, func):
     """The argument block of K9: score fp32 contiguous [B,h,w], labels int64 or uint8 contiguous [B,H,W], every size >= 1 and B H W, B h w < 2^31,
     func one of TAIL_FUNCS -> (B, h, w, H, W, bytes per label, func number)."""
     _chk(score, "score", dim=3)
-    _chk(labels, "labels", dtype=torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64, dim=3)
+    nb = _labels(labels)
     if func not in TAIL_FUNCS:
         raise RbaHipError(f"unknown func {func!r}; choose from {sorted(TAIL_FUNCS)}")
     (B, h, w), (H, W) = score.shape, labels.shape[1:]
     if labels.shape[0] != B or min(B, h, w, H, W) < 1 or max(B * H * W, B * h * w) >= 1 << 31:
         raise RbaHipError(f"outlier_tail: score [B,h,w] and labels [B,H,W] of one B, all sizes >= 1, B H W and B h w < 2^31; got "
                           f"{tuple(score.shape)} and {tuple(labels.shape)}")
-    return B, h, w, H, W, labels.element_size(), TAIL_FUNCS[func]
-
-
-def _outlier_tail_workspace(device, nbytes):
-    """outlier_tail's per-workgroup partial sums: per (device, stream) and grow-only like K1 / K4 backward's; the kernel writes every word it later reads."""
-    return _stream_workspace("outlier_tail", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+    return B, h, w, H, W, nb, TAIL_FUNCS[func]
 
 
 @_hip_op
@@ -944,9 +933,7 @@ def outlier_tail(score, labels, func, thr_in, thr_out):
     to the host; both results are bitwise reproducible from launch to launch."""
     B, h, w, H, W, nb, f = _outlier_tail_args(score, labels, func)
     dev = score.device
-    n = ctypes.c_int64(0)
-    _lib.check(_query("rba_outlier_tail_workspace_f32", B, H, W, ctypes.addressof(n)), "rba_outlier_tail_workspace_f32")
-    ws = _outlier_tail_workspace(dev, int(n.value))
+    ws, _ = _workspace("rba_outlier_tail_workspace_f32", "outlier_tail", dev, B, H, W)
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
     stats = torch.empty((4,), dtype=torch.float32, device=dev)
     _launch("rba_outlier_tail_fwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, f, float(thr_in), float(thr_out), _p(ws), _p(loss), _p(stats))
@@ -959,8 +946,7 @@ def outlier_tail_backward(score, labels, stats, grad_loss, func, thr_in, thr_out
     [B,h,w], bitwise reproducible from launch to launch; a score pixel no label pixel samples gets 0."""
     B, h, w, H, W, nb, f = _outlier_tail_args(score, labels, func)
     _shaped(stats, "stats", (4,))
-    if _chk(grad_loss, "grad_loss").numel() != 1:
-        raise RbaHipError(f"grad_loss must have one element, got shape {tuple(grad_loss.shape)}")
+    _one_element(grad_loss, "grad_loss")
     grad = torch.empty((B, h, w), dtype=torch.float32, device=score.device)
     _launch("rba_outlier_tail_bwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, f, float(thr_in), float(thr_out), _p(stats), _p(grad_loss),
             _p(grad))
@@ -972,7 +958,7 @@ def _dense_hybrid_loss_args(sem, ood, labels):
     [B,H,W], every size >= 1 and B H W, B K h w < 2^31 -> (B, K, h, w, H, W, bytes per label)."""
     _chk(sem, "sem", dim=4)
     _chk(ood, "ood", dim=4)
-    _chk(labels, "labels", dtype=torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64, dim=3)
+    nb = _labels(labels)
     (B, K, h, w), (H, W) = sem.shape, labels.shape[1:]
     if tuple(ood.shape) != (B, 2, h, w):
         raise RbaHipError(f"ood must have shape {(B, 2, h, w)} (sem is {tuple(sem.shape)}), got {tuple(ood.shape)}")
@@ -981,12 +967,7 @@ def _dense_hybrid_loss_args(sem, ood, labels):
     if labels.shape[0] != B or min(B, h, w, H, W) < 1 or max(B * H * W, B * K * h * w) >= 1 << 31:
         raise RbaHipError(f"dense_hybrid_loss: sem [B,K,h,w] and labels [B,H,W] of one B, all sizes >= 1, B H W and B K h w < 2^31; got "
                           f"{tuple(sem.shape)} and {tuple(labels.shape)}")
-    return B, K, h, w, H, W, labels.element_size()
-
-
-def _dense_hybrid_loss_workspace(device, nbytes):
-    """dense_hybrid_loss's per-workgroup partial sums: per (device, stream) and grow-only like K9's; the kernel writes every word it later reads."""
-    return _stream_workspace("dense_hybrid_loss", device, max(nbytes // 4, 1), torch.empty, torch.float32)
+    return B, K, h, w, H, W, nb
 
 
 @_hip_op
@@ -999,9 +980,7 @@ def dense_hybrid_loss(sem, ood, labels, beta):
     reproducible from launch to launch."""
     B, K, h, w, H, W, nb = _dense_hybrid_loss_args(sem, ood, labels)
     dev = sem.device
-    n = ctypes.c_int64(0)
-    _lib.check(_query("rba_dense_hybrid_loss_workspace_f32", B, H, W, ctypes.addressof(n)), "rba_dense_hybrid_loss_workspace_f32")
-    ws = _dense_hybrid_loss_workspace(dev, int(n.value))
+    ws, _ = _workspace("rba_dense_hybrid_loss_workspace_f32", "dense_hybrid_loss", dev, B, H, W)
     losses = torch.empty((4,), dtype=torch.float32, device=dev)
     stats = torch.empty((8,), dtype=torch.float32, device=dev)
     lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
@@ -1016,8 +995,7 @@ def dense_hybrid_loss_backward(sem, ood, labels, stats, lse, grad_loss, beta):
     B, K, h, w, H, W, nb = _dense_hybrid_loss_args(sem, ood, labels)
     _shaped(stats, "stats", (8,))
     _shaped(lse, "lse", (B, H, W))
-    if _chk(grad_loss, "grad_loss").numel() != 1:
-        raise RbaHipError(f"grad_loss must have one element, got shape {tuple(grad_loss.shape)}")
+    _one_element(grad_loss, "grad_loss")
     grad_sem = torch.empty((B, K, h, w), dtype=torch.float32, device=sem.device)
     grad_ood = torch.empty((B, 2, h, w), dtype=torch.float32, device=sem.device)
     _launch("rba_dense_hybrid_loss_bwd_f32", _p(sem), _p(ood), _p(labels), nb, _p(lse), B, K, h, w, H, W, float(beta), _p(stats), _p(grad_loss),
@@ -1025,28 +1003,18 @@ def dense_hybrid_loss_backward(sem, ood, labels, stats, lse, grad_loss, beta):
     return grad_sem, grad_ood
 
 
-def _label_dtype(labels):
-    return torch.uint8 if isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 else torch.int64
-
-
-def _one_element(t, name):
-    if _chk(t, name).numel() != 1:
-        raise RbaHipError(f"{name} must have one element, got shape {tuple(t.shape)}")
-    return t
-
-
 def _gambler_loss_args(sem, labels):
     """The argument block of K11a: sem fp32 contiguous [B,K+1,h,w] with 2 <= K + 1 <= 32, labels int64 or uint8 contiguous [B,H,W] with H, W >= 4
     (the blur's reflect padding), every other size >= 1, B <= 65535 and B H W, B (K+1) h w < 2^31 -> (B, K, h, w, H, W, bytes per label)."""
     _chk(sem, "sem", dim=4)
-    _chk(labels, "labels", dtype=_label_dtype(labels), dim=3)
+    nb = _labels(labels)
     (B, K1, h, w), (H, W) = sem.shape, labels.shape[1:]
     if not 2 <= K1 <= 32:
         raise RbaHipError(f"gambler_loss: 2 <= K + 1 <= 32 channels (the classes and the reservation channel), got {K1}")
     if labels.shape[0] != B or min(B, h, w) < 1 or min(H, W) < 4 or B > 65535 or max(B * H * W, B * K1 * h * w) >= 1 << 31:
         raise RbaHipError(f"gambler_loss: sem [B,K+1,h,w] and labels [B,H,W] of one B <= 65535, H and W >= 4, all other sizes >= 1, B H W and "
                           f"B (K+1) h w < 2^31; got {tuple(sem.shape)} and {tuple(labels.shape)}")
-    return B, K1 - 1, h, w, H, W, labels.element_size()
+    return B, K1 - 1, h, w, H, W, nb
 
 
 @_hip_op
@@ -1059,9 +1027,7 @@ def gambler_loss(sem, labels, ood_reg=0.1):
     back to the host; every result is bitwise reproducible from launch to launch."""
     B, K, h, w, H, W, nb = _gambler_loss_args(sem, labels)
     dev = sem.device
-    n = ctypes.c_int64(0)
-    _lib.check(_query("rba_gambler_loss_workspace_f32", B, H, W, ctypes.addressof(n)), "rba_gambler_loss_workspace_f32")
-    ws = _stream_workspace("gambler_loss", dev, max(int(n.value) // 4, 1), torch.empty, torch.float32)
+    ws, _ = _workspace("rba_gambler_loss_workspace_f32", "gambler_loss", dev, B, H, W)
     losses = torch.empty((3,), dtype=torch.float32, device=dev)
     stats = torch.empty((4,), dtype=torch.float32, device=dev)
     reward = torch.empty((B, H, W), dtype=torch.float32, device=dev)
@@ -1126,8 +1092,8 @@ def _score_reg_args(score, labels):
     B, h, w = score.shape
     H, W, nb = 1, 1, 8
     if labels is not None:
-        _chk(labels, "labels", dtype=_label_dtype(labels), dim=3)
-        H, W, nb = labels.shape[1], labels.shape[2], labels.element_size()
+        nb = _labels(labels)
+        H, W = labels.shape[1:]
         if labels.shape[0] != B:
             raise RbaHipError(f"score_reg: score [B,h,w] and labels [B,H,W] of one B; got {tuple(score.shape)} and {tuple(labels.shape)}")
     if min(B, h, w, H, W) < 1 or max(B * H * W, B * h * w) >= 1 << 31:
@@ -1143,9 +1109,7 @@ def score_reg(score, labels=None):
     stats [2] = the two sums, for the backward).  Nothing is read back; bitwise reproducible from launch to launch."""
     B, h, w, H, W, nb = _score_reg_args(score, labels)
     dev = score.device
-    n = ctypes.c_int64(0)
-    _lib.check(_query("rba_score_reg_workspace_f32", B, h, w, H, W, ctypes.addressof(n)), "rba_score_reg_workspace_f32")
-    ws = _stream_workspace("score_reg", dev, max(int(n.value) // 4, 1), torch.empty, torch.float32)
+    ws, _ = _workspace("rba_score_reg_workspace_f32", "score_reg", dev, B, h, w, H, W)
     losses = torch.empty((2,), dtype=torch.float32, device=dev)
     stats = torch.empty((2,), dtype=torch.float32, device=dev)
     _launch("rba_score_reg_fwd_f32", _p(score), _p(labels), nb, B, h, w, H, W, _p(ws), _p(losses), _p(stats))

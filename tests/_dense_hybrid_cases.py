@@ -71,6 +71,9 @@ def draw_labels(gen, B, K, H, W):
 # axis that does not resample; the template edges K = 20 | 21 and K = 32
 TAIL_SHAPES = ((1, 3, 7, 9, 25, 33), (2, 19, 16, 32, 64, 128), (1, 2, 9, 7, 4, 3), (1, 2, 1, 1, 5, 6), (1, 3, 3, 1, 3, 8),
                (1, 20, 8, 8, 32, 32), (1, 21, 8, 8, 32, 32), (1, 32, 4, 4, 9, 9))
+# two laps of the partial / finish reduction, a 16 x 16 class map under one large label map: 263 workgroups (the finishing workgroup's threads 0 .. 6
+# take a second record; a ragged last workgroup), and the 2048 cap (every partial thread walks a second pixel; the finish's eighth lap)
+LAP_SHAPES = ((1, 3, 16, 16, 261, 257), (1, 3, 16, 16, 725, 727))
 BETA = 0.03
 PART_NAMES = ("loss_seg", "loss_ood", "loss_th", "S_seg", "S_ood", "S_th", "S_x", "n_seg", "n_ood", "n_all", "m")
 
@@ -80,7 +83,7 @@ def tail_inputs(shape):
     """(sem [B,K,h,w] = 1.5 + 2 randn -- a positive mean, like the class map's, so that S_x and m are not sums that cancel to nothing --, ood
     [B,2,h,w] = 1.5 randn, labels [B,H,W] int64) on the CPU, seeded by the shape"""
     B, K, h, w, H, W = shape
-    gen = torch.Generator().manual_seed(10100 + TAIL_SHAPES.index(shape))
+    gen = torch.Generator().manual_seed(10100 + (TAIL_SHAPES + LAP_SHAPES).index(shape))
     sem = 1.5 + 2.0 * torch.randn(B, K, h, w, generator=gen)
     ood = 1.5 * torch.randn(B, 2, h, w, generator=gen)
     return sem, ood, draw_labels(gen, B, K, H, W)

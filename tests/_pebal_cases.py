@@ -173,6 +173,8 @@ def criterion_truth():
 # across one; the template edges K + 1 = 20 | 21 and K + 1 = 32
 TAIL_SHAPES = ((1, 3, 7, 9, 25, 33), (2, 19, 16, 32, 64, 128), (1, 2, 2, 3, 4, 4), (1, 2, 9, 7, 5, 6), (1, 2, 1, 1, 5, 6), (1, 3, 5, 20, 7, 70),
                (1, 19, 8, 8, 32, 32), (1, 20, 8, 8, 32, 32), (1, 31, 4, 4, 9, 9))
+# two laps of the partial / finish reduction (tests/_dense_hybrid_cases.py LAP_SHAPES): 263 workgroups, and the 2048 cap
+LAP_SHAPES = ((1, 3, 16, 16, 261, 257), (1, 3, 16, 16, 725, 727))
 MIN_R = 0.25
 
 
@@ -180,7 +182,7 @@ MIN_R = 0.25
 def tail_inputs(shape):
     """(sem [B,K+1,h,w] = 1.2 rand -- the class map's own range --, labels [B,H,W] int64: K10's draw) on the CPU, seeded by the shape"""
     B, K, h, w, H, W = shape
-    gen = torch.Generator().manual_seed(11100 + TAIL_SHAPES.index(shape))
+    gen = torch.Generator().manual_seed(11100 + (TAIL_SHAPES + LAP_SHAPES).index(shape))
     sem = 1.2 * torch.rand(B, K + 1, h, w, generator=gen)
     return sem, draw_labels(gen, B, K, H, W)
 
@@ -231,6 +233,7 @@ def blur_truth(shape):
 # ---------------------------------------------------------------------------------------------------------------- K11b
 # (B, h, w, H, W): K9's shapes -- a non-integer ratio; x4, two images; down-sampling; a single source pixel; axes that do not resample
 REG_SHAPES = ((1, 7, 9, 25, 33), (2, 32, 64, 128, 256), (1, 9, 7, 4, 3), (1, 1, 1, 5, 6), (1, 3, 1, 3, 8), (1, 1, 5, 1, 5))
+REG_LAP_SHAPES = ((1, 16, 16, 261, 257), (1, 16, 16, 725, 727))     # the same two laps for K11b
 REG_UPSTREAM = ((1.0, 0.0), (0.0, 1.0), (0.5, 2.0))                 # (d / d smoothness, d / d sparsity): each alone, both together
 
 
@@ -239,7 +242,7 @@ def reg_inputs(shape):
     """(score [B,h,w] = -(3 + randn), the energy score's range; labels [B,H,W] int64: 60 % inlier (0), 25 % outlier (1), 15 % void (255); a map of at
     most 32 pixels gets one outlier pixel whatever the draw) on the CPU"""
     B, h, w, H, W = shape
-    gen = torch.Generator().manual_seed(11400 + REG_SHAPES.index(shape))
+    gen = torch.Generator().manual_seed(11400 + (REG_SHAPES + REG_LAP_SHAPES).index(shape))
     score = -(3.0 + torch.randn(B, h, w, generator=gen))
     r = torch.rand(B, H, W, generator=gen)
     labels = torch.full((B, H, W), 255, dtype=torch.int64)

@@ -1517,7 +1517,7 @@ def test_k1_dynamic_tiles_match_static_and_workspace_self_resets(ops):
         r2 = ops.rba_reduce(mask, prob)[0]
     r1 = ops.rba_reduce(mask, prob)[0]
     torch.cuda.synchronize()
-    assert torch.equal(r1, static) and torch.equal(r2, static) and len(ops._K1_WORKSPACES) >= 2
+    assert torch.equal(r1, static) and torch.equal(r2, static) and len(ops._STREAM_WORKSPACES) >= 2
 
 
 # ----------------------------------------------------------------------------------- size-independent properties at BASELINE sizes

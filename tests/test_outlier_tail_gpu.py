@@ -15,6 +15,10 @@ pytestmark = pytest.mark.gpu
 THR_IN, THR_OUT = -1.0, -0.1
 # (B, h, w, H, W): a non-integer ratio; an exact x4 with two images; down-sampling (some score pixels get no gradient); single pixels; an axis that does not resample
 SHAPES = ((1, 7, 9, 25, 33), (2, 32, 64, 128, 256), (1, 9, 7, 4, 3), (1, 1, 1, 5, 6), (1, 5, 6, 1, 1), (1, 3, 1, 3, 8))
+# two laps of the partial / finish reduction, a 16 x 16 score under one large label map (four pixels to a thread before the cap): 259 workgroups (the
+# finishing workgroup's threads 0 .. 2 take a second record; a ragged last workgroup), and the 2048 cap (a partial thread walks a fifth pixel)
+LAP_SHAPES = ((1, 16, 16, 513, 515), (1, 16, 16, 1449, 1451))
+LAP_FUNCS = ("squared_hinge", "binary_cross_entropy")             # one of the thresholded terms, and the cross-entropy: the kernels' two forms
 UPSTREAM = (1.0, 2.0 ** -20)
 
 
@@ -61,7 +65,7 @@ def inputs(shape):
     side of each.  The three-value map (1,3,1,3,8) takes the first seed of its sequence whose draw does."""
     B, h, w, H, W = shape
     for k in range(64):
-        score, labels, classes, sides = _draw(shape, 9000 + SHAPES.index(shape) + 100 * k)
+        score, labels, classes, sides = _draw(shape, 9000 + (SHAPES + LAP_SHAPES).index(shape) + 100 * k)
         if classes and (sides or int((labels != 255).sum()) <= 16 or h * w == 1):
             return score, labels
     raise AssertionError(f"fixture: no draw of {shape} keeps both classes on both sides of their thresholds")
@@ -82,8 +86,11 @@ def truth(shape, func):
     return out
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
-@pytest.mark.parametrize("func", C.FUNCS)
+_id = lambda s: "x".join(map(str, s))
+
+
+@pytest.mark.parametrize("func,shape", [pytest.param(f, s, id=f"{f}-{_id(s)}") for s in SHAPES for f in C.FUNCS]
+                         + [pytest.param(f, s, id=f"{f}-{_id(s)}") for s in LAP_SHAPES for f in LAP_FUNCS])
 def test_kernel_against_fp64(shape, func):
     from rba_amd import ops
     score, labels = inputs(shape)

@@ -26,7 +26,7 @@ def _check_grad(what, g, g64, b):
         C.check(what, g.cpu(), g64, b)
 
 
-@pytest.mark.parametrize("shape", G.REG_SHAPES, ids=_id)
+@pytest.mark.parametrize("shape", G.REG_SHAPES + G.REG_LAP_SHAPES, ids=_id)
 def test_kernel_against_fp64(shape):
     from rba_amd import ops
     score, labels = G.reg_inputs(shape)
