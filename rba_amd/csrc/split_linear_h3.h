@@ -119,22 +119,44 @@ __device__ __forceinline__ void h3_epilogue(const f32x16_t (&accm)[CT], const f3
                                             float* C, const float* R, int M, int N, int m0, int n0, int BM, int BN, int wave, int l31,
                                             int lh, GnMoments gm = GnMoments{nullptr, 1, 1, 128}, float* sh = nullptr) {
   const bool interior = m0 + BM <= M && n0 + BN <= N;
+  const int rbase = m0 + 32 * wave + 4 * lh;
+  // Everything the epilogue reads from memory is requested here, for ALL column tiles at once (the k loop has released the operand registers): the tile loop
+  // below then waits for one round trip instead of one per column tile.  An interior tile's loads are unconditional (one uniform branch, no per-element test).
+  f32x16_t ress[RES ? CT : 1];
+  if (RES) {
+    if (interior) {
+#pragma unroll
+      for (int j = 0; j < CT; ++j) {
+        const float* src = R + (int64_t)rbase * N + (n0 + 32 * j + l31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ress[j][r] = src[(int64_t)(8 * (r >> 2) + (r & 3)) * N];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < CT; ++j) {
+        const int col = n0 + 32 * j + l31;
+        const float* src = R + (int64_t)rbase * N + col;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int ro = 8 * (r >> 2) + (r & 3);
+          ress[j][r] = (col < N && rbase + ro < M) ? src[(int64_t)ro * N] : 0.f;
+        }
+      }
+    }
+  }
+  float bvs[CT];
+#pragma unroll
+  for (int j = 0; j < CT; ++j) {
+    const int col = n0 + 32 * j + l31;
+    bvs[j] = (bias && col < N) ? bias[col] : 0.f;
+  }
   if (GNM) __syncthreads();                                                          // `sh` overlays the operand ring: every wave has left the k loop
 #pragma unroll
   for (int j = 0; j < CT; ++j) {
     const int col = n0 + 32 * j + l31;
-    const float bv = (bias && col < N) ? bias[col] : 0.f;
-    const int rbase = m0 + 32 * wave + 4 * lh;
+    const float bv = bvs[j];
     float* dst = C + (int64_t)rbase * N + col;
-    f32x16_t res;
-    if (RES) {
-      const float* src = R + (int64_t)rbase * N + col;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ro = 8 * (r >> 2) + (r & 3);
-        res[r] = (interior || (col < N && rbase + ro < M)) ? src[(int64_t)ro * N] : 0.f;
-      }
-    }
+    const f32x16_t& res = ress[RES ? j : 0];
     f32x16_t v;
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
@@ -209,11 +231,17 @@ template <int CT>
 __device__ __forceinline__ void h3_epilogue_nchw(const f32x16_t (&accm)[CT], const f32x16_t (&accl)[CT], const float* __restrict__ bias, float* C,
                                                  int M, int N, int P, int m0, int n0, int wave, int l31, int lh) {
   const bool vec = (P & 3) == 0;
+  float bvs[CT];                                                                   // all column tiles' bias values in one round trip (see h3_epilogue)
+#pragma unroll
+  for (int j = 0; j < CT; ++j) {
+    const int col = n0 + 32 * j + l31;
+    bvs[j] = (bias && col < N) ? bias[col] : 0.f;
+  }
 #pragma unroll
   for (int j = 0; j < CT; ++j) {
     const int col = n0 + 32 * j + l31;
     if (col >= N) continue;
-    const float bv = bias ? bias[col] : 0.f;
+    const float bv = bvs[j];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = m0 + 32 * wave + 8 * q + 4 * lh;
@@ -679,14 +707,22 @@ __device__ __forceinline__ void h3_epilogue_split(const f32x16_t (&accm)[CT], co
   const bool full = m0 + 128 <= M;                                                 // uniform
   const int NBo = N >> 5;
   char* base = reinterpret_cast<char*>(out_frag) + ((int64_t)((m0 >> 5) + wave) * NBo) * 4096 + l31 * 16 + lh * 1024;
+  // the lane's bias quads of every (column tile, register quad), requested together in front of the arithmetic: one round trip, not one per quad
+  f32x4 bvs[CT][4];
+#pragma unroll
+  for (int j = 0; j < CT; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = n0 + 32 * j + 8 * q + 4 * lh;
+      bvs[j][q] = (bias && n0 + 32 * j < N) ? *reinterpret_cast<const f32x4*>(bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
   for (int j = 0; j < CT; ++j) {
     const int nj = n0 + 32 * j;
     if (nj >= N) break;                                                            // uniform: whole 32-wide blocks only
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int n = nj + 8 * q + 4 * lh;
-      const f32x4 bv = bias ? *reinterpret_cast<const f32x4*>(bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      const f32x4 bv = bvs[j][q];
       f32x2 y0 = (f32x2){accl[j][4 * q], accl[j][4 * q + 1]} * 0.00048828125f + (f32x2){accm[j][4 * q], accm[j][4 * q + 1]};
       f32x2 y1 = (f32x2){accl[j][4 * q + 2], accl[j][4 * q + 3]} * 0.00048828125f + (f32x2){accm[j][4 * q + 2], accm[j][4 * q + 3]};
       y0 = y0 + (f32x2){bv.x, bv.y};
@@ -831,31 +867,57 @@ __global__ __launch_bounds__(h3_threads(FORM), h3_occupancy(FORM)) void split_li
     d[3] = img[SUBW + fb + 2 * BN + 64 * j];
   };
 
-  // CONVP: this lane's output pixel and the per-tap source row
-  int cpy = 0, cpx = 0, crow = 0, cNB = 1, cinv = 0;
+  // CONVP: the walk over (tap, channel block).  Per lane, ONCE: the output pixel's row and the nine taps that stay inside the image (cvalid, bit = tap).
+  // The walk itself is uniform: xloadset is called for c = 0, 1, 2, ... in order, so the channel block advances by a constant 4 KiB and only a change of
+  // tap (every Cin / 32 blocks) re-targets the lane's source row.  A lane whose tap leaves the image reads its OWN row (always a valid address) and
+  // carries one bit (cok[set]) to the block that consumes the set, where czero() zeroes the operands in front of that block's first MFMA -- the loads
+  // themselves have nothing behind them before the scheduling barrier and stay in flight across the MFMAs of the block that issued them.
+  int crow = 0, cNB = 1, ccb = 0, ctap = 0;
+  uint32_t cvalid = 0;
+  bool ctok = true, cok[2] = {true, true};
+  const char* csrc = nullptr;
+  auto ctarget = [&](int tap) {                                                    // tap is uniform: ky, dy, dx and the row step are scalars
+    const int ky = (tap * 11) >> 5, dy = ky - 1, dx = tap - 3 * ky - 1;              // tap / 3 for tap < 9
+    ctok = (cvalid >> tap) & 1u;
+    const int rs = ctok ? crow + dy * cs.W + dx : crow;
+    csrc = reinterpret_cast<const char*>(A) + ((int64_t)(rs >> 5) * cNB) * 4096 + (lh * 32 + (rs & 31)) * 16;
+  };
   if (CONVP) {
     crow = min(m0 + 32 * wave + l31, M - 1);
     const int pix = crow % (cs.H * cs.W);
-    cpy = pix / cs.W;
-    cpx = pix - cpy * cs.W;
+    const int cpy = pix / cs.W, cpx = pix - cpy * cs.W;
     cNB = cs.Cin >> 5;
-    cinv = (65536 + cNB - 1) / cNB;                                                // block / cNB == (block * cinv) >> 16 for block < 9 * cNB <= 576
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int dy = t / 3 - 1, dx = t % 3 - 1;
+      if ((unsigned)(cpy + dy) < (unsigned)cs.H && (unsigned)(cpx + dx) < (unsigned)cs.W) cvalid |= 1u << t;
+    }
+    ctarget(0);
   }
+  auto czero = [&](int p) {                                                        // exact selects: a NaN in the lane's own row does not reach the product
+    const f16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
+    ah[p][0] = cok[p] ? ah[p][0] : z;
+    al[p][0] = cok[p] ? al[p][0] : z;
+    ah[p][1] = cok[p] ? ah[p][1] : z;
+    al[p][1] = cok[p] ? al[p][1] : z;
+  };
+  auto cstep = [&](int c) {                                                        // csrc: block c - 1 -> block c; called at the head of block c - 1, in front of its weight loads,
+    if (c <= last) {                                                               // so that a change of tap waits for no load issued in this block
+      if (++ccb == cNB) {                                                          // (past the last block: the surplus load re-reads it, as bix() does)
+        ccb = 0;
+        ctarget(++ctap);
+      } else {
+        csrc += 4096;
+      }
+    }
+  };
   auto xloadset = [&](int c, int p) {
     if (CONVP) {
-      const int cc = bix(c);
-      const int tap = (cc * cinv) >> 16, cb = cc - tap * cNB;
-      const int ky = (tap * 11) >> 5, dy = ky - 1, dx = tap - 3 * ky - 1;              // tap / 3 for tap < 9
-      const bool ok = (unsigned)(cpy + dy) < (unsigned)cs.H && (unsigned)(cpx + dx) < (unsigned)cs.W;
-      const int rs = ok ? crow + dy * cs.W + dx : crow;
-      const char* src = reinterpret_cast<const char*>(A) + ((int64_t)(rs >> 5) * cNB + cb) * 4096 + (lh * 32 + (rs & 31)) * 16;
-      const f16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-      const f16x8_t v0 = *reinterpret_cast<const f16x8_t*>(src), v1 = *reinterpret_cast<const f16x8_t*>(src + 1024);
-      const f16x8_t v2 = *reinterpret_cast<const f16x8_t*>(src + 2048), v3 = *reinterpret_cast<const f16x8_t*>(src + 3072);
-      ah[p][0] = ok ? v0 : z;
-      al[p][0] = ok ? v1 : z;
-      ah[p][1] = ok ? v2 : z;
-      al[p][1] = ok ? v3 : z;
+      ah[p][0] = *reinterpret_cast<const f16x8_t*>(csrc);
+      al[p][0] = *reinterpret_cast<const f16x8_t*>(csrc + 1024);
+      ah[p][1] = *reinterpret_cast<const f16x8_t*>(csrc + 2048);
+      al[p][1] = *reinterpret_cast<const f16x8_t*>(csrc + 3072);
+      cok[p] = ctok;
       return;
     }
     const char* src = fbase + bix(c) * 4096;
@@ -937,6 +999,10 @@ __global__ __launch_bounds__(h3_threads(FORM), h3_occupancy(FORM)) void split_li
 #define RBA_XI(P) (DEEP ? (P) ^ 1 : 0)
 #define RBA_BLOCK(B, P, CUR, NXT)                                                                                       \
   {                                                                                                                     \
+    if (CONVP) {                                                                                                        \
+      czero(P);                                                                                                         \
+      cstep((B) + 1);                                                                                                   \
+    }                                                                                                                   \
     if (!(PROBE & 256)) { _Pragma("unroll") for (int q = 0; q < UPLW; ++q)(NXT)[wtid + 256 * RS * q] = wr[q]; }        \
     if (!(PROBE & 1)) wload((B) + 2);                                                                                   \
     if (DIRECT) xloadset((B) + 1, (P) ^ 1);                                                                             \

@@ -201,6 +201,14 @@ extern "C" int rba_split_linear_h3_timing(const float* x, const void* weight_pac
   else if (probe == 1500) rc = launch_h3p<1, H3_TIMING | H3_PRE | H3_FOUT>(a);            // round 4: the fc1 launch form (GELU, split image in and out), 128 x 128 tiles
   else if (probe == 1600) rc = launch_h3p<1, H3_TIMING | H3_PRE | H3_FOUT | H3_RS2>(a);   // ... and its 256 x 128 / 8-wave form (RS = 2)
   else if (probe == 1700) rc = launch_h3p<0, H3_TIMING | H3_PRE | H3_RS2>(a);             // RS = 2, fp32 rows out, no activation (the qkv launch form)
+  else if (probe == 1310 || probe == 1710) {                                              // the proj / fc2 launch forms: residual epilogue, in place over `out`
+    a.res = out;
+    rc = probe == 1310 ? launch_h3p<0, H3_TIMING | H3_PRE | H3_RES>(a) : launch_h3p<0, H3_TIMING | H3_PRE | H3_RES | H3_RS2>(a);
+  } else if (probe == 1800 || probe == 1810) {                                            // the FPN 3 x 3 convolution on a split image: ONE image of width 512, M = H * 512 rows, K = 9 Cin
+    if (M % 512) return (int)hipErrorInvalidValue;
+    a.cs = ConvShape{(int)(M / 512), 512, K / 9};
+    rc = probe == 1800 ? launch_h3p<0, H3_TIMING | H3_PRE | H3_CONVP | H3_RS2>(a) : launch_h3p<0, H3_TIMING | H3_PRE | H3_CONVP>(a);
+  }
   else if (probe == 1001) rc = launch_h3l<1, 4, H3_TIMING>(a);
   else rc = launch_h3<1, 4, H3_TIMING | h3_probe(127)>(a);
   return rba_gemm_status(rc);

@@ -10,7 +10,7 @@ import torch  # noqa: F401,E402  (its HIP runtime must be resident first, see rb
 
 from rba_amd import _lib, ops  # noqa: E402
 
-PATH = os.path.join(REPO, "rba_amd", "csrc", "tune", "librba_tune.so")
+PATH = os.environ.get("RBA_TUNE_LIB") or os.path.join(REPO, "rba_amd", "csrc", "tune", "librba_tune.so")   # env override: A/B runs of two builds
 _h = None
 
 

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Per-workgroup timeline of the f16x3 kernel (timing build): residency, prologue / loop / epilogue durations.
-  python tools/gemm_h3_timing.py M N K [probe]"""
+  python tools/gemm_h3_timing.py M N K [probe]
+probe (csrc/tune/split_linear_tune.hip, rba_split_linear_h3_timing): 0 plain kernel, 1000 / 11xx / 12xx pipelined on fp32 rows, 1300 / 1400 split image in,
+1500 / 1600 fc1 (GELU, split image out; 128 x 128 / 256 x 128), 1700 split image in on 256 x 128, 1310 / 1710 the same two with the residual epilogue,
+1800 / 1810 the 3 x 3 convolution on a split image (256 x 128 / 128 x 128; one image of width 512: M = H * 512, K = 9 Cin).
+RBA_TUNE_LIB=<path> times another build of the tune library (A/B of two builds in one call)."""
 import ctypes
 import os
 import sys
@@ -18,14 +22,16 @@ fn.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_int] * 3 + [c
 fn.restype = ctypes.c_int
 M, N, K = (int(v) for v in sys.argv[1:4])
 probe = int(sys.argv[4]) if len(sys.argv) > 4 else 0
-x = torch.randn(M, K, device="cuda")
-if probe in (1300, 1400, 1500, 1600, 1700):          # launch forms that read a split image
+CONV = (1800, 1810)                                  # 3 x 3 convolution over one image of width 512: M = H * 512 rows, K = 9 Cin
+ROWS256 = (1600, 1700, 1710, 1800)                   # 256 x 128 tiles
+x = torch.randn(M, K // 9 if probe in CONV else K, device="cuda")
+if probe in (1300, 1310, 1400, 1500, 1600, 1700, 1710) + CONV:          # launch forms that read a split image
     x = ops.SplitActivations.pack(x).data
 w = torch.randn(N, K, device="cuda") * K ** -0.5
 b = torch.randn(N, device="cuda")
 p3 = ops.split_weight(w, mode="f16x3")
-out = torch.empty(M, N, device="cuda")
-nwg = ((M + (255 if probe in (1600, 1700) else 127)) // (256 if probe in (1600, 1700) else 128)) * ((N + 127) // 128)
+out = torch.randn(M, N, device="cuda")               # (1310 / 1710: also the residual, updated in place)
+nwg = ((M + (255 if probe in ROWS256 else 127)) // (256 if probe in ROWS256 else 128)) * ((N + 127) // 128)
 dbg = torch.zeros(nwg * 6, dtype=torch.int64, device="cuda")
 for _ in range(3):
     rc = fn(x.data_ptr(), p3.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, probe, dbg.data_ptr(), torch.cuda.current_stream().cuda_stream)
