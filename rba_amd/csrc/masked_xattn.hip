@@ -161,7 +161,7 @@ __global__ __launch_bounds__(64 * WAVES) void xattn_partial_mfma_kernel(const fl
   }
   const bool use_mask = mlog != nullptr && qvalid && flag[b * Q + qt] != 0;
   const float* mrow = mlog ? mlog + ((int64_t)b * Q + (qvalid ? qt : 0)) * S : nullptr;
-  const bool vec_mask = (S & 3) == 0;
+  const bool vec_mask = (S & 3) == 0 && (((uintptr_t)mlog) & 15) == 0;      // 16-byte mask reads: every row starts on a 16-byte boundary
 
   float m_run = -INFINITY, l_run = 0.f;
   f32x4_x O0 = {0.f, 0.f, 0.f, 0.f}, O1 = O0;

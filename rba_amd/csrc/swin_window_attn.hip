@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64 * WAVES) void swin_window_attn_mfma_kernel(
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, kk = lane >> 4;
-  const bool vec_bias = (N & 3) == 0;
+  const bool vec_bias = (N & 3) == 0 && (((uintptr_t)bias) & 15) == 0;     // 16-byte reads of a rel_bias row: rows are N floats apart
 
   for (int strip = wave; strip < NT; strip += WAVES) {
     const int qt = strip * 16 + l15;                       // this lane's query (as B column / softmax owner)
@@ -392,7 +392,7 @@ extern "C" int rba_swin_window_attn_f32(const float* qkv, const float* qkv_bias,
   RBA_CHECK_ARG(ws >= 1 && ws * ws <= 256 && shift >= 0 && shift < ws);
   if (B == 0) return 0;
   RBA_CHECK_ARG(qkv && qkv_bias && bias && out);
-  RBA_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)qkv_bias | (uintptr_t)out) & 15) == 0);
+  RBA_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)qkv_bias | (uintptr_t)bias_frag | (uintptr_t)out) & 15) == 0);
   const int Hp = (H + ws - 1) / ws * ws, Wp = (W + ws - 1) / ws * ws;
   const int N = ws * ws;
   RBA_CHECK_ARG((int64_t)B * nH <= 65535 && Hp / ws <= 65535);
@@ -424,7 +424,7 @@ extern "C" int rba_swin_window_attn_split_out_f32(const float* qkv, const float*
   RBA_CHECK_ARG(B >= 0 && H >= 1 && W >= 1 && nH >= 1 && hd == 32 && ws == 12 && shift >= 0 && shift < ws);
   if (B == 0) return 0;
   RBA_CHECK_ARG(qkv && qkv_bias && bias_frag && out_frag);
-  RBA_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)qkv_bias | (uintptr_t)out_frag) & 15) == 0);
+  RBA_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)qkv_bias | (uintptr_t)bias_frag | (uintptr_t)out_frag) & 15) == 0);
   const int Hp = (H + ws - 1) / ws * ws, Wp = (W + ws - 1) / ws * ws;
   RBA_CHECK_ARG((int64_t)B * nH <= 65535 && Hp / ws <= 65535);
   rba_begin();

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WPE,
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, kk = lane >> 4;
-  const bool vec_bias = (N & 3) == 0;
+  const bool vec_bias = (N & 3) == 0 && (((uintptr_t)bias) & 15) == 0;     // 16-byte reads of a rel_bias row: rows are N floats apart
   // K fragment of key tile c: key c * 16 + l15, chunk kk -> byte offset (+ c * 1024)
   const int kfrag = l15 * 64 + ((kk ^ ((0x1320 >> (4 * ((l15 >> 2) & 3))) & 3)) * 16);
   // V transposing read of key tile c, d tile dt: rows c * 16 + 4 kk + (l15 >> 2) -> (+ c * 1024 + (dt ^ (kk & 1)) * 32)

@@ -214,11 +214,12 @@ def rba_reduce(mask_pred, cls_prob, want_sem_seg=False, want_argmax=False, score
     if cls_prob.shape[0] != Q:
         raise RbaHipError(f"cls_prob has {cls_prob.shape[0]} queries, mask_pred {Q}")
     K = cls_prob.shape[1]
+    mode = _mode(score)
     dev = mask_pred.device
     rba = torch.empty((H, W), dtype=torch.float32, device=dev)
     sem = torch.empty((K, H, W), dtype=torch.float32, device=dev) if want_sem_seg else None
     arg = torch.empty((H, W), dtype=torch.int32, device=dev) if want_argmax else None
-    _launch("rba_reduce_ws_f32", _p(mask_pred), _p(cls_prob), _p(rba), _p(sem), _p(arg), Q, K, H * W, _mode(score), _p(_k1_workspace(dev)))
+    _launch("rba_reduce_ws_f32", _p(mask_pred), _p(cls_prob), _p(rba), _p(sem), _p(arg), Q, K, H * W, mode, _p(_k1_workspace(dev)))
     return rba, sem, arg
 
 
@@ -229,13 +230,16 @@ def rba_reduce_up4(mask_lowres, cls_prob, crop_hw, want_sem_seg=False, want_argm
     _chk(mask_lowres, "mask_lowres", dim=3)
     _chk(cls_prob, "cls_prob", dim=2)
     Q, h, w = mask_lowres.shape
+    if cls_prob.shape[0] != Q:
+        raise RbaHipError(f"cls_prob has {cls_prob.shape[0]} queries, mask_lowres {Q}")
     K = cls_prob.shape[1]
     ch, cw = int(crop_hw[0]), int(crop_hw[1])
+    mode = _mode(score)
     dev = mask_lowres.device
     rba = torch.empty((ch, cw), dtype=torch.float32, device=dev)
     sem = torch.empty((K, ch, cw), dtype=torch.float32, device=dev) if want_sem_seg else None
     arg = torch.empty((ch, cw), dtype=torch.int32, device=dev) if want_argmax else None
-    _launch("rba_reduce_up4_f32", _p(mask_lowres), _p(cls_prob), _p(rba), _p(sem), _p(arg), Q, K, h, w, ch, cw, _mode(score))
+    _launch("rba_reduce_up4_f32", _p(mask_lowres), _p(cls_prob), _p(rba), _p(sem), _p(arg), Q, K, h, w, ch, cw, mode)
     return rba, sem, arg
 
 
@@ -489,6 +493,10 @@ def train_view(img, lab, params, obj=None, objmask=None, lut=None, ignore_label=
     v.new_h, v.new_w = int(params.new_h), int(params.new_w)
     if min(v.new_h, v.new_w) < 1:
         raise RbaHipError(f"train_view: empty resize target {(v.new_h, v.new_w)}")
+    v.y0, v.x0, v.ch, v.cw = (int(c) for c in params.crop)
+    v.pad_h, v.pad_w = (v.ch, v.cw) if pad_size is None else (int(pad_size[0]), int(pad_size[1]))
+    if min(v.ch, v.cw) < 1 or v.pad_h < v.ch or v.pad_w < v.cw:
+        raise RbaHipError(f"train_view: crop {(v.ch, v.cw)} and canvas {(v.pad_h, v.pad_w)}: the crop is non-empty and the canvas no smaller")
     tables = []                                                  # kept alive until the launch is enqueued
     if v.new_w != w:
         kx, bx, v.ksize_x = _pil_tables(dev, w, v.new_w)
@@ -502,11 +510,7 @@ def train_view(img, lab, params, obj=None, objmask=None, lut=None, ignore_label=
         ny, nx = _nearest_tables(dev, h, w, v.new_h, v.new_w)
         v.ny, v.nx = _p(ny), _p(nx)
         tables += [ny, nx]
-    v.y0, v.x0, v.ch, v.cw = (int(c) for c in params.crop)
-    v.pad_h, v.pad_w = (v.ch, v.cw) if pad_size is None else (int(pad_size[0]), int(pad_size[1]))
     v.flip, v.ignore_label, v.ood_label = int(bool(params.flip)), int(ignore_label), int(ood_label)
-    if min(v.ch, v.cw) < 1 or v.pad_h < v.ch or v.pad_w < v.cw:
-        raise RbaHipError(f"train_view: crop {(v.ch, v.cw)} and canvas {(v.pad_h, v.pad_w)}: the crop is non-empty and the canvas no smaller")
     c = params.color
     if c is not None:
         k = v.color
@@ -632,12 +636,19 @@ def clip_adamw_step(plan, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999
 CONFUSION_THREADS, CONFUSION_TILE, CONFUSION_GRID_CAP, CONFUSION_LDS_MAX_K = 256, 16, 512, 126
 
 
+def _level_shapes(spatial_shapes, L):
+    """spatial_shapes of multi-scale deformable attention: int64 [L, 2] = (h, w) per level (the kernels take a bare pointer and read 2 L values)."""
+    _chk(spatial_shapes, "spatial_shapes", torch.int64, 2)
+    if tuple(spatial_shapes.shape) != (L, 2):
+        raise RbaHipError(f"spatial_shapes must have shape {(L, 2)}, got {tuple(spatial_shapes.shape)}")
+    return spatial_shapes
+
+
 def _msda_args(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step, grad_output=None, backward=False):
     """The argument block of multi-scale deformable attention, forward and (``backward``: with grad_output) backward -> (dtype, N, S, M, D, L, Lq, P)."""
     # float or double, like the reference op (AT_DISPATCH_FLOATING_TYPES, ms_deform_attn_cuda.cu:69); all tensors of one type
     dt = value.dtype if isinstance(value, torch.Tensor) and value.dtype == torch.float64 else torch.float32
     _chk(value, "value", dt, dim=4)
-    _chk(spatial_shapes, "spatial_shapes", torch.int64, 2)
     _chk(level_start_index, "level_start_index", torch.int64, 1)
     _chk(sampling_locations, "sampling_loc", dt, dim=6)
     _chk(attention_weights, "attn_weight", dt, dim=5)
@@ -649,8 +660,9 @@ def _msda_args(value, spatial_shapes, level_start_index, sampling_locations, att
         raise RbaHipError("sampling_loc shape does not match value")
     if tuple(attention_weights.shape) != (N, Lq, M, L, P):
         raise RbaHipError("attn_weight shape does not match sampling_loc")
-    if spatial_shapes.shape[0] != L or level_start_index.shape[0] != L:
-        raise RbaHipError("spatial_shapes / level_start_index must have L rows")
+    _level_shapes(spatial_shapes, L)
+    if level_start_index.shape[0] != L:
+        raise RbaHipError("level_start_index must have L elements")
     if backward and tuple(grad_output.shape) != (N, Lq, M * D):
         raise RbaHipError(f"grad_output must have shape {(N, Lq, M * D)}, got {tuple(grad_output.shape)}")
     step = min(N, int(im2col_step))
@@ -1137,6 +1149,9 @@ def swin_bias_fragments(rel_bias, window_size):
     """[nH,N,N] gathered relative-position bias -> the MFMA-fragment-ordered copy K5 reads with coalesced loads."""
     _chk(rel_bias, "rel_bias", dim=3)
     nH = rel_bias.shape[0]
+    N = int(window_size) * int(window_size)
+    if window_size < 1 or tuple(rel_bias.shape) != (nH, N, N):
+        raise RbaHipError(f"rel_bias must be [nH, ws*ws, ws*ws] for window_size {window_size}, got {tuple(rel_bias.shape)}")
     frag = torch.empty(_query("rba_swin_bias_fragments_elems", nH, window_size), dtype=torch.float32, device=rel_bias.device)
     _launch("rba_swin_bias_fragments_f32", _p(rel_bias), _p(frag), nH, window_size)
     return frag
@@ -1298,9 +1313,9 @@ def msda_prepare(raw, reference_points, spatial_shapes, M, L, P):
     -> (sampling_locations [N,Lq,M,L,P,2], attention_weights [N,Lq,M,L,P]) as MSDeformAttn.forward computes them."""
     _chk(raw, "raw", dim=3)
     _chk(reference_points, "reference_points", dim=4)
-    _chk(spatial_shapes, "spatial_shapes", torch.int64, 2)
+    _level_shapes(spatial_shapes, L)
     N, Lq, W3 = raw.shape
-    if W3 != 3 * M * L * P or tuple(reference_points.shape) != (N, Lq, L, 2) or spatial_shapes.shape[0] != L:
+    if W3 != 3 * M * L * P or tuple(reference_points.shape) != (N, Lq, L, 2):
         raise RbaHipError("msda_prepare: shapes do not match")
     loc = torch.empty((N, Lq, M, L, P, 2), dtype=torch.float32, device=raw.device)
     attw = torch.empty((N, Lq, M, L, P), dtype=torch.float32, device=raw.device)
@@ -1320,14 +1335,14 @@ def msda_fused(value, spatial_shapes, level_start_index, raw, reference_points, 
     reference_points [N,Lq,L,2] -> [N,Lq,M*32]; sampling locations and the softmax over the L*P logits are computed inside the gather
     kernel (bit-identical to msda_prepare + ms_deform_attn_forward)."""
     _chk(value, "value", dim=4)
-    _chk(spatial_shapes, "spatial_shapes", torch.int64, 2)
+    _level_shapes(spatial_shapes, L)
     _chk(level_start_index, "level_start_index", torch.int64, 1)
     _chk(raw, "raw", dim=3)
     _chk(reference_points, "reference_points", dim=4)
     N, S, M2, D = value.shape
     _, Lq, W3 = raw.shape
     if (M2 != M or not msda_fused_ok(D, L, P, S, M) or W3 != 3 * M * L * P or raw.shape[0] != N or tuple(reference_points.shape) != (N, Lq, L, 2)
-            or spatial_shapes.shape[0] != L or level_start_index.shape[0] != L):
+            or level_start_index.shape[0] != L):
         raise RbaHipError("msda_fused: shapes do not match (head_dim 32, P = 4, L in {1, 3})")
     out = torch.empty((N, Lq, M * D), dtype=torch.float32, device=value.device)
     _launch("rba_msda_fused_f32", _p(value), _p(spatial_shapes), _p(level_start_index), _p(raw), _p(reference_points), _p(out), N, S, M, D, L, Lq, P)
@@ -1616,6 +1631,8 @@ def mlp_fused(x, fc1, fc2, residual):
     if (x.shape[-1] != C or tuple(fc2.weight.shape) != (C, hidden) or tuple(residual.shape) != tuple(x.shape) or C != 128 or hidden % 32
             or _split_mode() != "f16x3"):
         raise RbaHipError("mlp_fused needs C == 128, hidden % 32 == 0, matching fc1 / fc2 and the f16x3 mode")
+    _vec(fc1.bias, "fc1.bias", hidden)
+    _vec(fc2.bias, "fc2.bias", C, optional=True)
     _launch("rba_swin_mlp_fused_f16x3_f32", _p(x), _p(_cached_planes(fc1, fc1.weight)), _p(fc1.bias), _p(_cached_planes(fc2, fc2.weight)), _p(fc2.bias),
             _p(residual), _p(residual), M, C, hidden)
     return residual
@@ -1633,6 +1650,8 @@ def mlp_fused_ln(x, norm, fc1, fc2):
     M = x.numel() // C
     if x.shape[-1] != C or tuple(fc2.weight.shape) != (C, hidden) or C != 128 or hidden % 32 or _split_mode() != "f16x3":
         raise RbaHipError("mlp_fused_ln needs C == 128, hidden % 32 == 0, matching fc1 / fc2 and the f16x3 mode")
+    _vec(fc1.bias, "fc1.bias", hidden)
+    _vec(fc2.bias, "fc2.bias", C, optional=True)
     _launch("rba_swin_mlp_fused_ln_f16x3_f32", _p(x), _p(g), _p(b), float(eps), _p(_cached_planes(fc1, fc1.weight)), _p(fc1.bias),
             _p(_cached_planes(fc2, fc2.weight)), _p(fc2.bias), M, C, hidden)
     return x
@@ -1732,7 +1751,7 @@ def linear_gn_stats(x, lin, num_groups, eps, rows_per_image, use_bias=True):
     M = x.numel() // K
     if not linear_emits_gn_moments(M, N, K, rows_per_image, num_groups) or x.shape[-1] != K:
         raise RbaHipError("linear_gn_stats: check linear_emits_gn_moments(M, N, K, rows_per_image, G) first")
-    bias = lin.bias if use_bias else None
+    bias = _vec(lin.bias if use_bias else None, "bias", N, optional=True)
     planes = _cached_planes(lin, w)
     B, splits = M // rows_per_image, rows_per_image // 128
     out = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=torch.float32, device=x.device)
