@@ -91,53 +91,9 @@ class MaskedXattnFunction(Function):
         return ops.masked_xattn_backward(q, k, v, mask_logits, grad_out, *need) + (None,)
 
 
-class _HeadLayerNormFunction(Function):
-    """``decoder_norm`` of the differentiable last head call: forward = the kernel of the inference path (``ops.add_layer_norm``), backward = torch's
-    LayerNorm backward on the [B*Q, C] query tensor, for weight and bias only -- the decoder-layer output receives no gradient."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps):
-        ctx.eps = eps
-        ctx.save_for_backward(x, weight, bias)
-        return ops.add_layer_norm(x, weight, bias, eps)[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_y):
-        x, weight, bias = ctx.saved_tensors
-        with torch.enable_grad():
-            w, b = weight.detach().requires_grad_(True), bias.detach().requires_grad_(True)
-            y = F.layer_norm(x, (x.shape[-1],), w, b, ctx.eps)
-        gw, gb = torch.autograd.grad(y, (w, b), grad_y)
-        return None, gw, gb, None
-
-
-class _HeadLinearFunction(Function):
-    """A query-side Linear (+ ReLU) of the differentiable last head call: forward = ``_qlinear`` (the skinny exact-fp32 kernel of the inference
-    path), backward = three small library GEMMs on [B*Q, C] rows by design, as in ``MSDeformAttn._forward_differentiable``."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        y = _qlinear(x, weight, bias, relu)
-        ctx.relu = relu
-        ctx.save_for_backward(x, weight, y if relu else None)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_y):
-        x, weight, y = ctx.saved_tensors
-        g = grad_y.reshape(-1, grad_y.shape[-1])
-        if ctx.relu:
-            g = g * (y.reshape(g.shape) > 0)
-        gx = (g @ weight).view(x.shape) if ctx.needs_input_grad[0] else None
-        gw = g.t() @ x.reshape(-1, x.shape[-1]) if ctx.needs_input_grad[1] else None
-        return gx, gw, g.sum(0) if ctx.needs_input_grad[2] else None, None
-
-
-# ------------------------------------------------------------------------------------------------ the differentiable decoder layers
-# (``MultiScaleMaskedTransformerDecoder.differentiable_decoder``): every forward below is the inference path's launch, so the values are its
-# bits; the backwards are small library GEMMs on [B*Q, C] rows by design, as `_HeadLinearFunction`'s, and K3's backward kernel for the core.
+# ------------------------------------------------------------------------------------------------ the query-side operations of a training forward
+# Every forward below is the inference path's launch, so the values are its bits; the backwards are small library GEMMs / torch's LayerNorm
+# backward on [B*Q, C] rows by design, as in ``MSDeformAttn._forward_differentiable``, and K3's backward kernel for the core.
 def _rows(t):
     return t.reshape(-1, t.shape[-1])
 
@@ -196,7 +152,7 @@ class _KVFunction(Function):
     @staticmethod
     def forward(ctx, mha, key, key_add, level_row, weight, bias):
         ctx.save_for_backward(key, key_add, weight)
-        return mha._project_kv(key, key, key_add)
+        return mha._project_kv(key, key_add)
 
     @staticmethod
     @once_differentiable
@@ -241,6 +197,23 @@ class _AddLayerNormFunction(Function):
                 gw if need[3] else None, gb if need[4] else None, None)
 
 
+# One body per layer: `graph` (always the caller's explicit argument, never read off requires_grad or grad mode) picks the autograd Function
+# around the launch; without it the launch is called directly and no Function.apply is entered.
+def _linear(graph, x, weight, bias=None, relu=False, x_add=None):
+    return _LinearFunction.apply(x, x_add, weight, bias, relu) if graph else _qlinear(x, weight, bias, relu, x_add)
+
+
+def _add_layer_norm(graph, x, norm, residual=None, residual_bias=None):
+    """norm(x + residual + residual_bias): the folded bias (out_proj.bias / linear2.bias) is added inside the launch"""
+    if graph:
+        return _AddLayerNormFunction.apply(x, residual, residual_bias, norm.weight, norm.bias, norm.eps)
+    return ops.add_layer_norm(x, norm.weight, norm.bias, norm.eps, residual, residual_bias)[1]
+
+
+def _masked_xattn(graph, q, k, v, mask_logits):
+    return MaskedXattnFunction.apply(q, k, v, mask_logits) if graph else ops.masked_xattn(q, k, v, mask_logits)
+
+
 class _MHAParams(nn.Module):
     """Parameter holder with nn.MultiheadAttention's names: in_proj_weight, in_proj_bias, out_proj.{weight,bias}."""
 
@@ -257,37 +230,42 @@ class _MHAParams(nn.Module):
         return derived(self, "kv_views", (w, b),
                        lambda: (SimpleNamespace(weight=w[E:2 * E], bias=b[E:2 * E]), SimpleNamespace(weight=w[2 * E:], bias=b[2 * E:])))
 
-    def forward(self, query, key, value, mask_logits=None, key_add=None, query_add=None):
-        """batch-first: query [B,Q,E], key/value [B,S,E]; mask_logits [B,Q,S] (blocked iff sigmoid < 0.5).  key_add / query_add: the keys /
-        queries are ``key + key_add`` / ``query + query_add`` (position embeddings, :48-58, :106-118), added inside the projections."""
+    def forward(self, query, key, mask_logits=None, key_add=None, query_add=None, level_row=None, graph=False):
+        """batch-first: query [B,Q,E], key [B,S,E] (the values too); mask_logits [B,Q,S] (blocked iff sigmoid < 0.5).  key_add / query_add: the
+        keys / queries are ``key + key_add`` / ``query + query_add`` (position embeddings, :48-58, :106-118), added inside the projections.
+        graph: the same launches with an autograd graph over query, key, the position operands and the four parameters (the mask logits get
+        no gradient); level_row: see `_KVFunction`."""
         E, nH = self.embed_dim, self.num_heads
         B, Q, _ = query.shape
         S = key.shape[1]
         w, b = self.in_proj_weight, self.in_proj_bias
-        if (query is key and key is value and key_add is query_add and B * Q <= 128 and E % 32 == 0 and E % 16 == 0
-                and w.is_contiguous() and query.is_contiguous()):
+        if query is key and key_add is query_add and B * Q <= 128 and E % 32 == 0 and w.is_contiguous() and query.is_contiguous():
             # self-attention: q = W_q (tgt + pos), k = W_k (tgt + pos), v = W_v tgt -- ONE launch over the stacked in_proj weight (was: an add
             # and three launches); q, k, v come back separately contiguous
-            q, k, v = ops.skinny_linear(query, w, b, x_add=None if query_add is None else query_add.contiguous(), add_cols=2 * E, segments=3)
-            o = ops.masked_xattn(q.view(B, Q, nH, E // nH), k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH), mask_logits)
-            return _qlinear(o, self.out_proj.weight)
-        q = _qlinear(query, w[:E], b[:E], x_add=query_add).view(B, Q, nH, E // nH)
-        k, v = self._project_kv(key, value, key_add)
-        o = ops.masked_xattn(q, k, v, mask_logits)
-        return _qlinear(o, self.out_proj.weight)            # out_proj.bias is added inside the caller's fused add+LN
+            if graph:
+                q, k, v = _QKVFunction.apply(query, query_add, w, b)
+            else:
+                q, k, v = ops.skinny_linear(query, w, b, x_add=None if query_add is None else query_add.contiguous(), add_cols=2 * E, segments=3)
+            k, v = k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH)
+        else:
+            q = _linear(graph, query, w[:E], b[:E], x_add=query_add)
+            k, v = _KVFunction.apply(self, key, key_add, level_row, w, b) if graph else self._project_kv(key, key_add)
+        o = _masked_xattn(graph, q.view(B, Q, nH, E // nH), k, v, mask_logits)
+        return _linear(graph, o, self.out_proj.weight)      # out_proj.bias is added inside the caller's fused add+LN
 
-    def _project_kv(self, key, value, key_add):
-        """k = W_k (key + key_add) + b_k, v = W_v value + b_v as [B,S,nH,hd], by the kernel that pays for the shape"""
+    def _project_kv(self, key, key_add):
+        """k = W_k (key + key_add) + b_k, v = W_v key + b_v as [B,S,nH,hd], by the kernel that pays for the shape"""
         E, nH = self.embed_dim, self.num_heads
         B, S, _ = key.shape
         w, b = self.in_proj_weight, self.in_proj_bias
-        if (key is value and B * S > 128 and key.is_contiguous() and ops.token_linear_pays(B * S, E, E)
+        if (B * S > 128 and key.is_contiguous() and ops.token_linear_pays(B * S, E, E)
                 and (key_add is None or (key_add.is_contiguous() and tuple(key_add.shape) == tuple(key.shape)))):
             # cross-attention: k = W_k (memory + pos) + b_k and v = W_v memory + b_v in ONE launch of the row-complete kernel (was: an add and two
             # library GEMMs per layer)
             lk, lv = self._kv_views()
             k, v = ops.token_linear_multi(key, [(lk, key_add, None, 0, False), (lv, None, None, 0, False)])
             return k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH)
+        value = key
         if key_add is not None:
             key = key + key_add
         if B * S > 128:
@@ -298,41 +276,19 @@ class _MHAParams(nn.Module):
         # self-attention: key / value are the (<= 128) queries themselves -> the skinny kernel too (hipBLASLt takes 33 us for 100 x 256 x 256)
         return _qlinear(key, w[E:2 * E], b[E:2 * E]).view(B, S, nH, E // nH), _qlinear(value, w[2 * E:], b[2 * E:]).view(B, S, nH, E // nH)
 
-    def forward_differentiable(self, query, key, mask_logits=None, key_add=None, query_add=None, level_row=None):
-        """`forward(query, key, key, ...)` -- the same launches in the same order, the same bits -- with an autograd graph over query, key, the
-        position operands and the four parameters; the mask logits get no gradient.  level_row: see `_KVFunction`."""
-        E, nH = self.embed_dim, self.num_heads
-        B, Q, _ = query.shape
-        S = key.shape[1]
-        w, b = self.in_proj_weight, self.in_proj_bias
-        if (query is key and key_add is query_add and B * Q <= 128 and E % 32 == 0 and E % 16 == 0
-                and w.is_contiguous() and query.is_contiguous()):
-            q, k, v = _QKVFunction.apply(query, query_add, w, b)
-            k, v = k.view(B, S, nH, E // nH), v.view(B, S, nH, E // nH)
-        else:
-            q = _LinearFunction.apply(query, query_add, w[:E], b[:E], False)
-            k, v = _KVFunction.apply(self, key, key_add, level_row, w, b)
-        o = MaskedXattnFunction.apply(q.view(B, Q, nH, E // nH), k, v, mask_logits)
-        return _LinearFunction.apply(o, None, self.out_proj.weight, None, False)
 
-
+# The three decoder layers (post-norm).  graph: the same launches in the same order -- the same bits -- with an autograd graph over tgt, query_pos
+# and the layer's parameters.
 class SelfAttentionLayer(nn.Module):
     def __init__(self, d_model, nhead):
         super().__init__()
         self.self_attn = _MHAParams(d_model, nhead)
         self.norm = nn.LayerNorm(d_model)
 
-    def forward(self, tgt, query_pos):
+    def forward(self, tgt, query_pos, graph=False):
         tgt = tgt.contiguous()
-        t2 = self.self_attn(tgt, tgt, tgt, key_add=query_pos, query_add=query_pos)      # q = k = tgt + query_pos, v = tgt
-        return ops.add_layer_norm(tgt.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps, t2,
-                                  self.self_attn.out_proj.bias)[1]          # forward_post :48-58
-
-    def forward_differentiable(self, tgt, query_pos):
-        """forward's launches and bits, with an autograd graph over tgt, query_pos and the layer's parameters"""
-        tgt = tgt.contiguous()
-        t2 = self.self_attn.forward_differentiable(tgt, tgt, key_add=query_pos, query_add=query_pos)
-        return _AddLayerNormFunction.apply(tgt, t2, self.self_attn.out_proj.bias, self.norm.weight, self.norm.bias, self.norm.eps)
+        t2 = self.self_attn(tgt, tgt, key_add=query_pos, query_add=query_pos, graph=graph)      # q = k = tgt + query_pos, v = tgt
+        return _add_layer_norm(graph, tgt, self.norm, t2, self.self_attn.out_proj.bias)          # forward_post :48-58
 
 
 class CrossAttentionLayer(nn.Module):
@@ -341,17 +297,11 @@ class CrossAttentionLayer(nn.Module):
         self.multihead_attn = _MHAParams(d_model, nhead)
         self.norm = nn.LayerNorm(d_model)
 
-    def forward(self, tgt, memory, mask_logits, pos, query_pos):
-        t2 = self.multihead_attn(tgt, memory, memory, mask_logits, key_add=pos, query_add=query_pos)
-        return ops.add_layer_norm(tgt.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps, t2,
-                                  self.multihead_attn.out_proj.bias)[1]     # forward_post :106-118
-
-    def forward_differentiable(self, tgt, memory, mask_logits, pos, query_pos, level_row=None):
-        """forward's launches and bits, with an autograd graph over tgt, query_pos and the layer's parameters (memory too where it requires grad);
-        level_row: a vector already added to every row of `memory` that is to receive its gradient (`_KVFunction`)"""
-        m = self.multihead_attn
-        t2 = m.forward_differentiable(tgt, memory, mask_logits, key_add=pos, query_add=query_pos, level_row=level_row)
-        return _AddLayerNormFunction.apply(tgt.contiguous(), t2, m.out_proj.bias, self.norm.weight, self.norm.bias, self.norm.eps)
+    def forward(self, tgt, memory, mask_logits, pos, query_pos, level_row=None, graph=False):
+        """level_row (graph only): a vector already added to every row of `memory` that is to receive its gradient (`_KVFunction`); memory
+        itself gets one where it requires grad"""
+        t2 = self.multihead_attn(tgt, memory, mask_logits, key_add=pos, query_add=query_pos, level_row=level_row, graph=graph)
+        return _add_layer_norm(graph, tgt.contiguous(), self.norm, t2, self.multihead_attn.out_proj.bias)     # forward_post :106-118
 
 
 class FFNLayer(nn.Module):
@@ -361,16 +311,9 @@ class FFNLayer(nn.Module):
         self.linear2 = nn.Linear(dim_feedforward, d_model)
         self.norm = nn.LayerNorm(d_model)
 
-    def forward(self, tgt):
-        t2 = _qlinear(_qlinear(tgt, self.linear1.weight, self.linear1.bias, relu=True), self.linear2.weight)
-        return ops.add_layer_norm(tgt.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps, t2,
-                                  self.linear2.bias)[1]                     # forward_post :171-175
-
-    def forward_differentiable(self, tgt):
-        """forward's launches and bits, with an autograd graph over tgt and the layer's parameters"""
-        h = _LinearFunction.apply(tgt, None, self.linear1.weight, self.linear1.bias, True)
-        t2 = _LinearFunction.apply(h, None, self.linear2.weight, None, False)
-        return _AddLayerNormFunction.apply(tgt.contiguous(), t2, self.linear2.bias, self.norm.weight, self.norm.bias, self.norm.eps)
+    def forward(self, tgt, graph=False):
+        t2 = _linear(graph, _linear(graph, tgt, self.linear1.weight, self.linear1.bias, relu=True), self.linear2.weight)
+        return _add_layer_norm(graph, tgt.contiguous(), self.norm, t2, self.linear2.bias)         # forward_post :171-175
 
 
 class MLP(nn.Module):
@@ -380,9 +323,9 @@ class MLP(nn.Module):
         h = [hidden_dim] * (num_layers - 1)
         self.layers = nn.ModuleList(nn.Linear(n, k) for n, k in zip([input_dim] + h, h + [output_dim]))
 
-    def forward(self, x):
+    def forward(self, x, graph=False):
         for i, layer in enumerate(self.layers):
-            x = _qlinear(x, layer.weight, layer.bias, relu=i < self.num_layers - 1)
+            x = _linear(graph, x, layer.weight, layer.bias, relu=i < self.num_layers - 1)
         return x
 
 
@@ -416,36 +359,31 @@ class BNReluConv(nn.Module):
 
 @TRANSFORMER_DECODER_REGISTRY.register()
 class MultiScaleMaskedTransformerDecoder(nn.Module):
-    """``differentiable_heads`` (attribute, default False) is the explicit opt-in to the outlier-supervised fine-tune, which trains the two
-    prediction heads only (FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP): with it set and grad mode on, the LAST ``forward_prediction_heads`` call of
-    ``forward`` (reference :472-479) builds an autograd graph over ``decoder_norm.{weight,bias}``, ``class_embed.{weight,bias}`` and the six
-    ``mask_embed`` tensors.  Its forward runs the kernels of the inference path -- ``pred_logits`` and ``pred_masks`` are bit-identical to it -- and
-    the contraction's backward is K4's backward kernel (``MaskLogitsFunction``).  ``mask_features`` and the decoder-layer output entering that
-    call receive no gradient: everything upstream of it runs under ``torch.no_grad`` and is not differentiable in this library; ``aux_outputs``
-    stay as in inference (detached; ``pred_logits`` only on the sparse path) unless ``deep_supervision`` is set too.  Otherwise -- whatever
-    ``self.training`` or ``requires_grad`` of the parameters say -- the inference path runs, which builds no autograd graph.
+    """``forward`` runs in one of three modes, decided once at its top from two attributes (both default False) and grad mode.  In every mode each
+    layer and head is the one body that launches the inference kernels in the inference order, so ``pred_logits`` and ``pred_masks`` are the
+    inference forward's bits; a training mode only wraps those launches in autograd Functions.  ``mask_features`` and the memory never receive
+    a gradient (frozen pixel decoder), nor do the attention-mask logits (reference :487): their head calls stay sparse, under ``no_grad``.
 
-    ``deep_supervision`` (attribute, default False; read only with ``differentiable_heads`` set and grad mode on) is the recipe's
-    DEEP_SUPERVISION: ``aux_outputs`` then has ``num_layers`` entries in the reference's ``_set_aux_loss`` order -- the head call before layer 0,
-    then the calls after layers 0 ... L-2 -- each with ``pred_logits`` and a dense ``pred_masks`` [B,Q,H/4,W/4] that carry a graph over the same
-    ten head tensors and nothing else.  Decoding is untouched (under ``no_grad``, sparse intermediate heads, the attention masks and final
-    outputs of inference); the differentiable evaluations are added behind it on the decoder-layer outputs it held at each head call, and
-    their values are the bits the inference forward returns with ``sparse_intermediate_heads = False``.
+    None -- inference: no autograd graph is built, whatever ``self.training`` or ``requires_grad`` of the parameters say.
+    "heads" -- ``differentiable_heads`` set and grad mode on: the outlier-supervised fine-tune of the two prediction heads
+      (FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP).  Decoding runs under ``no_grad`` as in inference; the LAST ``forward_prediction_heads`` call
+      (reference :472-479) builds a graph over ``decoder_norm.{weight,bias}``, ``class_embed.{weight,bias}`` and the six ``mask_embed`` tensors,
+      not over the decoder-layer output entering it.  The contraction's backward is K4's backward kernel (``MaskLogitsFunction``).
+    "decoder" -- ``differentiable_decoder`` set too: the released PEBAL recipe, which freezes the backbone and the pixel decoder and nothing
+      else.  The decoder layers carry a graph over every predictor parameter that requires grad (cross-attention, self-attention, FFN, their
+      norms, ``query_feat``, ``query_embed``, ``level_embed``), and the head calls that return outputs are differentiable with respect to the
+      layer output too.  The attention core's backward is K3's backward kernel, the Linears' and norms' are library GEMMs / torch's LayerNorm
+      backward on [B*Q, C] rows.  The cached initial head call is bypassed.
 
-    ``differentiable_ood_head`` (attribute, default False; read only with ``differentiable_heads`` set and grad mode on, on a model with the
-    DenseHybrid head) is the DenseHybrid recipe's FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP_AND_OOD_PRED: ``out["ood_pred"]`` is then computed in plain
-    torch on the detached ``mask_features`` (``BNReluConv.forward_differentiable``) and carries a graph over the head's four parameters --
-    ``ood_pred.norm.{weight,bias}``, ``ood_pred.conv.{weight,bias}`` -- and nothing else; the batch norm runs in the mode ``ood_pred.norm.training``
-    says and updates its running statistics in training mode.  Without it ``ood_pred`` stays the inference kernel's output under ``no_grad``.
-
-    ``differentiable_decoder`` (attribute, default False; read only with ``differentiable_heads`` set and grad mode on) trains the whole decoder --
-    the released PEBAL recipe, which freezes the backbone and the pixel decoder and nothing else: ``_decode_differentiable`` runs the decoder layers
-    with an autograd graph over every predictor parameter that requires grad (cross-attention, self-attention, FFN, their norms, ``query_feat``,
-    ``query_embed``, ``level_embed``) and the head calls that return outputs are differentiable with respect to the layer output too.  The forward
-    launches the inference kernels in the inference order (``pred_logits``, ``pred_masks`` and the ``aux_outputs`` are the bits of an inference
-    forward with ``sparse_intermediate_heads = False``); the attention core's backward is K3's backward kernel, the Linears' and norms' are library
-    GEMMs / torch's LayerNorm backward on [B*Q, C] rows.  The memory and ``mask_features`` are detached (frozen pixel decoder), the attention-mask
-    logits get no gradient (reference :487) and their head calls stay sparse under ``no_grad``; the cached initial head call is bypassed."""
+    Two more attributes (default False) are read only in a training mode.  ``deep_supervision`` (the recipe's DEEP_SUPERVISION): ``aux_outputs``
+    has ``num_layers`` entries in the reference's ``_set_aux_loss`` order -- the head call before layer 0, then the calls after layers 0 ... L-2
+    -- each with ``pred_logits`` and a dense ``pred_masks`` [B,Q,H/4,W/4] carrying the graph of the mode.  They are evaluated behind the
+    untouched decoding, on the decoder-layer outputs it held at each head call, and their values are the bits the inference forward returns with
+    ``sparse_intermediate_heads = False``; without it ``aux_outputs`` stay as in inference (detached; ``pred_logits`` only on the sparse path).
+    ``differentiable_ood_head`` (the DenseHybrid recipe's FREEZE_TRANSFORMER_DECODER_EXCEPT_MLP_AND_OOD_PRED, on a model with that head):
+    ``out["ood_pred"]`` is computed in plain torch on the detached ``mask_features`` (``BNReluConv.forward_differentiable``) with a graph over
+    ``ood_pred.norm.{weight,bias}`` and ``ood_pred.conv.{weight,bias}`` only; the batch norm runs in the mode ``ood_pred.norm.training`` says and
+    updates its running statistics in training mode.  Without it ``ood_pred`` stays the inference kernel's output under ``no_grad``."""
 
     differentiable_heads = False
     deep_supervision = False
@@ -540,32 +478,22 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             return False
         return ops.composed_mask_head_pays(mask_features.rows_per_image, sum(r.data.shape[1] for r in rows))
 
-    def _query_side_heads(self, output):
-        """decoder_norm -> class_embed, mask_embed MLP on the query tensor [B,Q,C] (reference :473-476): (class logits [B,Q,K+1], mask embedding [B,Q,md])"""
-        dec = ops.add_layer_norm(output.contiguous(), self.decoder_norm.weight, self.decoder_norm.bias, self.decoder_norm.eps)[1]
-        return _qlinear(dec, self.class_embed.weight, self.class_embed.bias), self.mask_embed(dec).contiguous()
+    def _query_side_heads(self, output, mode=None):
+        """decoder_norm -> class_embed, mask_embed MLP on the query tensor [B,Q,C] (reference :473-476): (class logits [B,Q,K+1], mask embedding [B,Q,md]).
+        mode (forward()'s): the same launches in the same order with an autograd graph over the ten head tensors -- "decoder": over `output` too."""
+        graph = mode is not None
+        if mode == "heads":
+            output = output.detach()
+        dec = _add_layer_norm(graph, output.contiguous(), self.decoder_norm)
+        return _linear(graph, dec, self.class_embed.weight, self.class_embed.bias), self.mask_embed(dec, graph).contiguous()
 
-    def _query_side_heads_differentiable(self, output, through=False):
-        """_query_side_heads with an autograd graph over its ten parameters (not over `output` unless `through`: the differentiable decoder):
-        the same launches in the same order"""
-        n = self.decoder_norm
-        if through:
-            dec = _AddLayerNormFunction.apply(output.contiguous(), None, None, n.weight, n.bias, n.eps)
-        else:
-            dec = _HeadLayerNormFunction.apply(output.detach().contiguous(), n.weight, n.bias, n.eps)
-        outputs_class = _HeadLinearFunction.apply(dec, self.class_embed.weight, self.class_embed.bias, False)
-        e = dec
-        for i, layer in enumerate(self.mask_embed.layers):
-            e = _HeadLinearFunction.apply(e, layer.weight, layer.bias, i < self.mask_embed.num_layers - 1)
-        return outputs_class, e.contiguous()
-
-    def _aux_heads_differentiable(self, outputs, mask_features, through=False):
+    def _aux_heads_differentiable(self, outputs, mask_features, mode):
         """The intermediate head calls of deep supervision on `outputs` = the decoder-layer outputs [B,Q,C] entering them: the query side once on
         their concatenation along the batch axis (row-wise kernels: the bits of one call each, and one backward pass), then one contraction per
         call against the one `mask_features` -> [{"pred_logits", "pred_masks"}], every tensor with a graph over the ten head tensors only
-        (`through`: over `outputs` too)."""
+        (mode "decoder": over `outputs` too)."""
         B = outputs[0].shape[0]
-        cls, embed = self._query_side_heads_differentiable(torch.cat(outputs, dim=0), through)
+        cls, embed = self._query_side_heads(torch.cat(outputs, dim=0), mode)
         feat = mask_features.detach()
         return [{"pred_logits": cls[l * B:(l + 1) * B], "pred_masks": MaskLogitsFunction.apply(embed[l * B:(l + 1) * B], feat)}
                 for l in range(len(outputs))]
@@ -595,14 +523,14 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         return cache.get(key, build)
 
     def forward_prediction_heads(self, output, mask_features, attn_mask_target_size, need_attn_mask=True, need_masks=True,
-                                 gathered=None, query_side=None):
+                                 gathered=None, query_side=None, mode=None):
         """output [B,Q,C] -> class logits [B,Q,K+1], mask logits [B,Q,H/4,W/4] (None unless need_masks), attention-mask
         logits [B,Q,h*w] (reference :472-489; the threshold itself happens inside K3).  When only the attention mask is
         consumed (every call but the last) the mask logits are evaluated just at the 2x2 source pixels each attention
-        cell interpolates -- the same arithmetic on 4*h*w instead of H*W/16 columns."""
-        if self.differentiable_heads and torch.is_grad_enabled() and need_masks and not need_attn_mask:
-            # the last call of a fine-tune forward (see the class): live heads, never the cached initial ones
-            outputs_class, mask_embed = self._query_side_heads_differentiable(output)
+        cell interpolates -- the same arithmetic on 4*h*w instead of H*W/16 columns.  mode: forward()'s, for its last call."""
+        if mode is not None:
+            # the last call of a training forward (see the class): live heads, never the cached initial ones
+            outputs_class, mask_embed = self._query_side_heads(output, mode)
             return outputs_class, MaskLogitsFunction.apply(mask_embed, mask_features.detach()), None
         if query_side is not None:
             outputs_class, mask_embed = query_side
@@ -644,32 +572,26 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
 
     def forward(self, x, mask_features, mask=None):
         """x: list of [B,C,h_l,w_l]; mask_features [B,md,H/4,W/4] -> dict(pred_logits, pred_masks, aux_outputs)
-        (reference :398-470).  With ``differentiable_heads`` and grad mode on, everything but the last head call runs under no_grad; with
-        ``deep_supervision`` too, the intermediate head calls are evaluated once more behind it, differentiably (see the class)."""
+        (reference :398-470).  The mode (see the class) is decided here, once, and passed down: nothing below reads the flags or grad mode."""
         assert len(x) == self.num_feature_levels
         del mask
-        differentiable = self.differentiable_heads and torch.is_grad_enabled()
-        frozen = torch.no_grad if differentiable else contextlib.nullcontext
-        if differentiable and isinstance(mask_features, DeferredMaskFeatures):
-            # decided HERE: inside frozen() grad mode reads off.  The differentiable last call wants the map (MaskLogitsFunction), as before
-            mask_features = mask_features.materialize()
-        through = differentiable and self.differentiable_decoder
-        if through:
-            output, mask_features, predictions_class, predictions_mask, head_inputs = self._decode_differentiable(x, mask_features)
-            cls, embed = self._query_side_heads_differentiable(output, through=True)
-            msk = MaskLogitsFunction.apply(embed, mask_features)
-        else:
-            with frozen():
-                output, mask_features, side, predictions_class, predictions_mask, head_inputs = self._decode(x, mask_features)
-            cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side)
-        if differentiable and self.deep_supervision:
-            aux = self._aux_heads_differentiable(head_inputs, mask_features, through) if head_inputs else []
+        mode = None
+        if self.differentiable_heads and torch.is_grad_enabled():
+            mode = "decoder" if self.differentiable_decoder else "heads"
+        frozen = contextlib.nullcontext if mode is None else torch.no_grad
+        if mode is not None and isinstance(mask_features, DeferredMaskFeatures):
+            mask_features = mask_features.materialize()               # the differentiable last call wants the map (MaskLogitsFunction)
+        with (torch.no_grad if mode == "heads" else contextlib.nullcontext)():
+            output, mask_features, side, predictions_class, predictions_mask, head_inputs = self._decode(x, mask_features, mode == "decoder")
+        cls, msk, _ = self.forward_prediction_heads(output, mask_features, None, need_attn_mask=False, need_masks=True, query_side=side, mode=mode)
+        if mode is not None and self.deep_supervision:
+            aux = self._aux_heads_differentiable(head_inputs, mask_features, mode) if head_inputs else []
         else:
             aux = [({"pred_logits": a, "pred_masks": b} if b is not None else {"pred_logits": a})
                    for a, b in zip(predictions_class, predictions_mask)]
         out = {"pred_logits": cls, "pred_masks": msk, "aux_outputs": aux}
         if self.ood_prediction:
-            if differentiable and self.differentiable_ood_head:
+            if mode is not None and self.differentiable_ood_head:
                 out["ood_pred"] = self.ood_pred.forward_differentiable(mask_features.detach())
             else:
                 with frozen():
@@ -688,77 +610,52 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             src.append(tok + self.level_embed.weight[i])                                      # [B,S,C] contiguous (:424-426)
         return src, pos, size_list
 
-    def _decode_differentiable(self, x, mask_features):
-        """`_decode` with an autograd graph over the decoder layers (``differentiable_decoder``; see the class) -> (decoder-layer output [B,Q,C],
-        detached contiguous mask_features, class / mask predictions of the intermediate calls as in `_decode` (detached), the decoder-layer outputs
-        that entered those calls (with their graph)).  The same launches in the same order as `_decode` without the cached initial heads."""
-        B = x[0].shape[0]
-        with torch.no_grad():
-            src, pos, size_list = self._memory_tokens(x)                # frozen pixel decoder: no gradient to the memory; level_embed's own goes
-            mask_features = mask_features.detach().contiguous()         # through `level_row` below
-        train_level = self.level_embed.weight.requires_grad
-        query_embed = self.query_embed.weight[None].expand(B, -1, -1)
-        output = self.query_feat.weight[None].expand(B, -1, -1).contiguous()
-        predictions_class, predictions_mask, head_inputs = [], [], []
-        gathered = {}
-
-        def attn_mask_head(out, level):
-            with torch.no_grad():                                       # the mask is detached in the reference (:487): sparse, as in inference
-                c, m, logits = self.forward_prediction_heads(out.detach(), mask_features, size_list[level], True, need_masks=False, gathered=gathered)
-            predictions_class.append(c)
-            predictions_mask.append(m)
-            head_inputs.append(out)
-            return logits
-
-        if self.num_layers == 0:
-            return output, mask_features, predictions_class, predictions_mask, head_inputs
-        attn_logits = attn_mask_head(output, 0)
-        for i in range(self.num_layers):
-            li = i % self.num_feature_levels
-            output = self.transformer_cross_attention_layers[i].forward_differentiable(
-                output, src[li], attn_logits, pos[li], query_embed, self.level_embed.weight[li] if train_level else None)
-            output = self.transformer_self_attention_layers[i].forward_differentiable(output, query_embed)
-            output = self.transformer_ffn_layers[i].forward_differentiable(output)
-            if i == self.num_layers - 1:
-                break
-            attn_logits = attn_mask_head(output, (i + 1) % self.num_feature_levels)
-        return output, mask_features, predictions_class, predictions_mask, head_inputs
-
-    def _decode(self, x, mask_features):
+    def _decode(self, x, mask_features, graph=False):
         """Everything of forward before its last head call -> (decoder-layer output [B,Q,C], contiguous mask_features, the cached query side of that
         call (only a decoder without layers has one), class and mask predictions of the intermediate calls, the decoder-layer outputs that entered
-        those calls)."""
-        src, pos, size_list = self._memory_tokens(x)
+        those calls).  graph: the same launches in the same order with an autograd graph over the decoder layers -- the memory is built under
+        no_grad and `mask_features` detached (frozen pixel decoder; level_embed's own gradient goes through `level_row`), the cached initial heads
+        are bypassed, and the intermediate head calls run under no_grad on the detached layer output (the mask is detached in the reference,
+        :487), sparse as in inference; the returned decoder-layer outputs carry their graph."""
+        frozen = torch.no_grad if graph else contextlib.nullcontext
+        with frozen():
+            src, pos, size_list = self._memory_tokens(x)
         B = x[0].shape[0]
         query_embed = self.query_embed.weight[None].expand(B, -1, -1)
-        first = self._initial_query_side(B, mask_features.device) if self.cache_initial_heads else None
+        first = self._initial_query_side(B, mask_features.device) if self.cache_initial_heads and not graph else None
         if first is not None:
             output, side0 = first                                     # constants of the checkpoint (never written: every layer returns new tensors)
         else:
             output, side0 = self.query_feat.weight[None].expand(B, -1, -1).contiguous(), None
-        if isinstance(mask_features, DeferredMaskFeatures) and not self._composed_mask_heads(mask_features, size_list):
+        if graph:
+            mask_features = mask_features.detach()                    # (forward() has materialised it)
+        elif isinstance(mask_features, DeferredMaskFeatures) and not self._composed_mask_heads(mask_features, size_list):
             mask_features = mask_features.materialize()               # today's path from here on, bit for bit
         if not isinstance(mask_features, DeferredMaskFeatures):
             mask_features = mask_features.contiguous()
+        level_row = graph and self.level_embed.weight.requires_grad
         predictions_class, predictions_mask, head_inputs = [], [], []
-        if self.num_layers == 0:
-            return output, mask_features, side0, predictions_class, predictions_mask, head_inputs
         gathered = {}
-        cls, msk, attn_logits = self.forward_prediction_heads(output, mask_features, size_list[0], True, need_masks=False, gathered=gathered,
-                                                              query_side=side0)
-        predictions_class.append(cls)
-        predictions_mask.append(msk)
-        head_inputs.append(output)
-        for i in range(self.num_layers):
-            li = i % self.num_feature_levels
-            output = self.transformer_cross_attention_layers[i](output, src[li], attn_logits, pos[li], query_embed)   # memory + pos: inside the key projection
-            output = self.transformer_self_attention_layers[i](output, query_embed)
-            output = self.transformer_ffn_layers[i](output)
-            if i == self.num_layers - 1:
-                break
-            cls, msk, attn_logits = self.forward_prediction_heads(
-                output, mask_features, size_list[(i + 1) % self.num_feature_levels], need_attn_mask=True, need_masks=False, gathered=gathered)
+
+        def attn_mask_head(out, level, side=None):
+            with frozen():
+                cls, msk, logits = self.forward_prediction_heads(out.detach() if graph else out, mask_features, size_list[level], need_attn_mask=True,
+                                                                 need_masks=False, gathered=gathered, query_side=side)
             predictions_class.append(cls)
             predictions_mask.append(msk)
-            head_inputs.append(output)
+            head_inputs.append(out)
+            return logits
+
+        if self.num_layers == 0:
+            return output, mask_features, side0, predictions_class, predictions_mask, head_inputs
+        attn_logits = attn_mask_head(output, 0, side0)
+        for i in range(self.num_layers):
+            li = i % self.num_feature_levels
+            output = self.transformer_cross_attention_layers[i](output, src[li], attn_logits, pos[li], query_embed,     # memory + pos: inside the key projection
+                                                                self.level_embed.weight[li] if level_row else None, graph)
+            output = self.transformer_self_attention_layers[i](output, query_embed, graph)
+            output = self.transformer_ffn_layers[i](output, graph)
+            if i == self.num_layers - 1:
+                break
+            attn_logits = attn_mask_head(output, (i + 1) % self.num_feature_levels)
         return output, mask_features, None, predictions_class, predictions_mask, head_inputs

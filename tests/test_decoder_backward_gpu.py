@@ -41,7 +41,7 @@ def compare(what, got, t64, t32):
 
 
 # ---------------------------------------------------------------------------------------------- each layer type at the released widths
-def _layer(kind):
+def _layer(kind, B=B, S=S):
     from rba_amd.modeling.transformer_decoder import mask2former_transformer_decoder as M
     layer = {"cross": lambda: M.CrossAttentionLayer(D, NH), "self": lambda: M.SelfAttentionLayer(D, NH), "ffn": lambda: M.FFNLayer(D, FFN)}[kind]()
     g = torch.Generator().manual_seed(31)
@@ -81,21 +81,61 @@ def _oracle_layer(kind, layer, inp, dtype):
     return grads
 
 
-@pytest.mark.parametrize("kind", ["cross", "self", "ffn"])
-def test_layer_at_released_widths(kind):
-    layer, inp = _layer(kind)
+def _layer_args(kind, inp):
+    return {"cross": lambda: (dev(inp["mem"]), dev(inp["ml"]), dev(inp["pos"]), dev(inp["qpos"])), "self": lambda: (dev(inp["qpos"]),), "ffn": lambda: ()}[kind]()
+
+
+# self at B = 1 is the stacked in_proj in one launch (B Q <= 128); at B = 2 the split projections
+@pytest.mark.parametrize("kind, batch", [pytest.param("cross", 2, id="cross"), pytest.param("self", 2, id="self"), pytest.param("ffn", 2, id="ffn"),
+                                         pytest.param("self", 1, id="self-B1")])
+def test_layer_at_released_widths(kind, batch):
+    layer, inp = _layer(kind, batch)
     t64, t32 = _oracle_layer(kind, layer, inp, torch.float64), _oracle_layer(kind, layer, inp, torch.float32)
     layer = layer.cuda()
     tgt = dev(inp["tgt"]).requires_grad_(True)
-    args = {"cross": lambda: (dev(inp["mem"]), dev(inp["ml"]), dev(inp["pos"]), dev(inp["qpos"])), "self": lambda: (dev(inp["qpos"]),), "ffn": lambda: ()}[kind]()
+    args = _layer_args(kind, inp)
     with torch.no_grad():
         want = layer(tgt, *args)
-    out = layer.forward_differentiable(tgt, *args)
+    out = layer(tgt, *args, graph=True)
     assert torch.equal(out, want) and out.grad_fn is not None
     out.backward(dev(inp["go"]))
     got = {k: p.grad for k, p in layer.named_parameters()}
     got["tgt"] = tgt.grad
     compare(kind, got, t64, t32)
+
+
+def _recorded_launches(monkeypatch):
+    """the list that receives the entry-point name of every kernel launch from here on"""
+    from rba_amd import ops
+    names, launch = [], ops._launch
+
+    def recording(name, *args, **kwargs):
+        names.append(name)
+        return launch(name, *args, **kwargs)
+
+    monkeypatch.setattr(ops, "_launch", recording)
+    return names
+
+
+@pytest.mark.parametrize("kind, batch, keys", [("self", 1, S), ("self", 2, S), ("cross", 2, 512), ("cross", 1, 64), ("ffn", 2, S)])
+def test_a_layers_training_forward_is_its_inference_launches(kind, batch, keys, monkeypatch):
+    """graph=True wraps the launches of the inference body in autograd Functions and adds, drops or reorders none: self with the stacked in_proj
+    (B Q <= 128) and with split projections, cross with the row-complete key / value launch and on the skinny route (B S <= 128), ffn"""
+    layer, inp = _layer(kind, batch, keys)
+    layer = layer.cuda()
+    tgt = dev(inp["tgt"]).requires_grad_(True)
+    args = _layer_args(kind, inp)
+    with torch.no_grad():
+        layer(tgt, *args)                                    # unrecorded: a first forward also packs the weight images it caches
+    names = _recorded_launches(monkeypatch)
+    with torch.no_grad():
+        layer(tgt, *args)
+    inference = list(names)
+    del names[:]
+    out = layer(tgt, *args, graph=True)
+    assert out.grad_fn is not None
+    print(kind, batch, keys, inference)
+    assert inference and names == inference
 
 
 # ---------------------------------------------------------------------------------------------- the whole decoder
@@ -172,6 +212,21 @@ def test_heads_only_guard():
     unset = run(False, False)
     for n, g in unset.items():
         assert (g is not None) == (n.split(".")[0] in heads), n
+
+
+def test_inference_builds_no_graph(monkeypatch):
+    """all four flags off: a forward with grad mode on and every parameter requiring grad is still the inference path"""
+    a, sd, x, mf = problem("tiny3")[:4]
+    pred = predictor(a, sd)
+    for p in pred.parameters():
+        p.requires_grad_(True)
+    assert not (pred.differentiable_heads or pred.deep_supervision or pred.differentiable_ood_head or pred.differentiable_decoder)
+    names = _recorded_launches(monkeypatch)
+    assert torch.is_grad_enabled()
+    out = pred([dev(t) for t in x], dev(mf))
+    tensors = [out["pred_logits"], out["pred_masks"]] + [v for aux in out["aux_outputs"] for v in aux.values()]
+    assert len(out["aux_outputs"]) == a["dec_layers"] and all(t.grad_fn is None for t in tensors)
+    assert names and not {"rba_masked_xattn_bwd_f32", "rba_mask_logits_bwd_f32"} & set(names)
 
 
 def test_finetune_outputs_refuses_the_flag_alone():
