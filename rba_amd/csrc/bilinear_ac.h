@@ -15,7 +15,11 @@ struct AcTap {
 __host__ __device__ __forceinline__ float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 __device__ __forceinline__ AcTap tap_of(int dst, float scale, int in) {
-  const float src = scale * (float)dst;
+  // the product rounded ONCE, for the floor and for the weight alike: written as scale * dst, -ffp-contract=fast fused it into `l` below in some
+  // callers (K10 / K11a's backward) and not in others -- fma(scale, dst, -i0) is one ulp of src away from src - i0, so a tap whose weight is exactly 0
+  // in torch (src an integer) got about -2^-22 there, and a backward's weights were no longer its forward's bits.  An fma with +0 is not a product
+  // the compiler may contract (it would have to prove the product is not -0).
+  const float src = fmaf(scale, (float)dst, 0.0f);
   int i0 = (int)src;                                    // src >= 0: trunc == floor
   i0 = i0 < in - 1 ? i0 : in - 1;                       // never past the map, whatever the product's rounding
   AcTap t;

@@ -52,7 +52,12 @@ def case_inputs(name):
     """(E [B,Q,C], F [B,C,N], G [B,Q,N]) fp32 on the CPU, seeded by the case: G = randn * rand(Q,1) * 1e-3 (the size of a mean's gradient, a
     different weight per query), F = 0.25 randn with channel 0 constant 1, E = randn"""
     _, B, Q, C, N = CASE[name]
-    gen = torch.Generator().manual_seed(4000 + NAMES.index(name))
+    return inputs_for(B, Q, C, N, 4000 + NAMES.index(name))
+
+
+def inputs_for(B, Q, C, N, seed):
+    """`case_inputs` for any shape, seeded: the named cases and the random-shape sweep draw here"""
+    gen = torch.Generator().manual_seed(seed)
     G = torch.randn(B, Q, N, generator=gen) * torch.rand(B, Q, 1, generator=gen) * 1e-3
     Fm = 0.25 * torch.randn(B, C, N, generator=gen)
     Fm[:, 0] = 1.0

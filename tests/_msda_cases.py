@@ -67,7 +67,11 @@ def outside(loc, shapes):
 
 def make(name, dtype, seed=7):
     """-> dict(value, shapes [L,2] int64, lsi [L] int64, loc, w, go), CPU tensors of `dtype`"""
-    N, M, D, Lq, shapes, P, kind = CASES[name]
+    return make_shape(*CASES[name], dtype, seed)
+
+
+def make_shape(N, M, D, Lq, shapes, P, kind, dtype, seed):
+    """`make` for any shape (the named cases and the random-shape sweep draw here)"""
     g = torch.Generator().manual_seed(seed)
     L = len(shapes)
     S = sum(h * w for h, w in shapes)

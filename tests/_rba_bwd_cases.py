@@ -62,22 +62,28 @@ CASES = (
     ("bigq", 250, 19, 515, SCORES, 6.0, None),
     ("quarter", 100, 19, 131072, ("rba",), 6.0, None),
     ("saturated", 100, 19, 4096, SCORES, 40.0, 120.0),
+    ("k27", 100, 27, 515, SCORES, 6.0, None),                   # 20 < K <= 32: the launcher's third template instantiation, chunked (Q + K > 124)
 )
 CASE = {c[0]: c for c in CASES}
 CASE_MODES = [(c[0], s) for c in CASES for s in c[4]]
 
 
-@functools.lru_cache(maxsize=None)
-def case_inputs(name):
-    """(mask [Q,N], prob [Q,K], g [N]) fp32 on the CPU, seeded by the case"""
-    _, Q, K, N, _, scale, clip = CASE[name]
-    gen = torch.Generator().manual_seed(1000 + [c[0] for c in CASES].index(name))
+def inputs_for(Q, K, N, scale, seed, clip=None):
+    """(mask [Q,N], prob [Q,K], g [N]) fp32 on the CPU for any shape, seeded: the named cases and the random-shape sweep draw here"""
+    gen = torch.Generator().manual_seed(seed)
     mask = scale * torch.randn(Q, N, generator=gen)
     if clip is not None:
         mask = mask.clamp(-clip, clip)
     prob = F.softmax(2.0 * torch.randn(Q, K + 1, generator=gen), dim=-1)[:, :-1].contiguous()
     g = torch.randn(N, generator=gen)
     return mask, prob, g
+
+
+@functools.lru_cache(maxsize=None)
+def case_inputs(name):
+    """(mask [Q,N], prob [Q,K], g [N]) fp32 on the CPU, seeded by the case"""
+    _, Q, K, N, _, scale, clip = CASE[name]
+    return inputs_for(Q, K, N, scale, 1000 + [c[0] for c in CASES].index(name), clip)
 
 
 def _autograd(mask, prob, g, score):

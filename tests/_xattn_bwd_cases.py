@@ -40,13 +40,19 @@ def make(name, zero_col=None, seed=None):
     open, where S > 300 row 2 open only in its last 150 keys; the others randn * 3.  zero_col = s: no fully blocked row, and key s is blocked in
     every row instead."""
     B, Q, S, nH, masked = CASES[name]
-    g = torch.Generator().manual_seed(Q + S if seed is None else seed)
+    return make_shape(B, Q, S, nH, masked, Q + S if seed is None else seed, zero_col=zero_col)
+
+
+def make_shape(B, Q, S, nH, masked, seed, zero_col=None, blocked_row=None):
+    """`make` for any shape (the named cases and the random-shape sweep draw here).  blocked_row: whether row 0 is fully blocked; None = as
+    `make` plants it, exactly when no zero_col is given.  The sweep plants both (zero_col with blocked_row=True)."""
+    g = torch.Generator().manual_seed(seed)
     q, k, v = (torch.randn(B, n, nH, 32, generator=g) for n in (Q, S, S))
     go = torch.randn(B, Q, nH * 32, generator=g)
     ml = None
     if masked:
         ml = torch.randn(B, Q, S, generator=g) * 3
-        if zero_col is None:
+        if zero_col is None if blocked_row is None else blocked_row:
             ml[:, 0] = -5.0
         if Q > 1:
             ml[:, 1] = 5.0

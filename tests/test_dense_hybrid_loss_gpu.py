@@ -24,7 +24,7 @@ def _poison():
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("shape", D.TAIL_SHAPES + D.LAP_SHAPES, ids=_id)
+@pytest.mark.parametrize("shape", D.TAIL_SHAPES + D.LAP_SHAPES + D.FOUND_SHAPES, ids=_id)
 def test_kernel_against_fp64(shape):
     from rba_amd import ops
     sem, ood, labels = D.tail_inputs(shape)

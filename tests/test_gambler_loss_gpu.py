@@ -34,7 +34,7 @@ def _check_forward(losses, stats, R, t):
     C.check("R", R.cpu(), p64["R"], C.err(p32["R"], p64["R"]))
 
 
-@pytest.mark.parametrize("shape", G.TAIL_SHAPES + G.LAP_SHAPES, ids=_id)
+@pytest.mark.parametrize("shape", G.TAIL_SHAPES + G.LAP_SHAPES + G.FOUND_SHAPES, ids=_id)
 def test_kernel_against_fp64(shape):
     from rba_amd import ops
     sem, labels = G.tail_inputs(shape)

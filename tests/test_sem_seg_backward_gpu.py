@@ -10,7 +10,7 @@ from tests import _rba_bwd_cases as C
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("base", "odd", "one", "mapillary", "kmax", "bigq")        # resident and chunked (kmax, bigq) forms, every KMAX instantiation
+NAMES = ("base", "odd", "one", "mapillary", "kmax", "bigq", "k27")  # resident and chunked (kmax, bigq, k27) forms, every KMAX instantiation (20, 80, 160, 32)
 
 
 @functools.lru_cache(maxsize=None)
