@@ -67,6 +67,9 @@
  *   rba_gaussian_blur_f32       <- transforms.GaussianBlur(7, sigma=1) on the anomaly map (support.py:366-383)
  *   rba_threshold_u8 / rba_morph3x3_u8 / rba_ccl4_roots_i32 <- the open-set branch of MaskFormer.panoptic_inference
  *                                  (maskformer_model.py:454-481: threshold, cv2.morphologyEx open/close, cv2.connectedComponents)
+ *   rba_panoptic_merge_f32 / rba_panoptic_merge_up4_f32 / rba_panoptic_assign_i32 <- the closed-set merge of MaskFormer.panoptic_inference
+ *                                  (maskformer_model.py:395-452: sigmoid, score product, argmax, the per-query area tests' sums, the id writes)
+ *   rba_segment_pairs_accum     <- pq_compute_single_core's np.unique(pan_gt * OFFSET + pan_pred) (mask2former/evaluation/evaluation.py:152-159)
  *   rba_add_layer_norm_f32      <- `x = x + proj(...)` followed by nn.LayerNorm (swin.py:284-293 and the post-norm layers
  *                                  of msdeformattn.py:134-138, mask2former_transformer_decoder.py:48-58,106-118,171-175)
  *   rba_group_norm_f32          <- GroupNorm(32) [+ ReLU] behind Detectron2's Conv2d(norm=get_norm("GN"), activation)
@@ -812,6 +815,38 @@ typedef struct {               /* one step's scalars, read on the host */
 int rba_clip_adamw_step_f32(const rba_adamw_tensor* tensors, const int32_t* blocks /* [n_blocks][2] */, int n_blocks, int chunk, const float* grad,
                             float* exp_avg, float* exp_avg_sq, const float* partials, int n_partials, const rba_adamw_hyper* hyper /* host */,
                             float* stats /* [1] */, void* stream);
+
+/* K16a.  The closed-set panoptic merge (maskformer_model.py:395-452) for every kept query in one pass over the mask logits.
+ * mask [Q,HW] mask logits at the output resolution; score [Q] = the queries' class scores; keep [Q] uint8, non-zero = the query competes.
+ * Per pixel p, over the kept q in ascending order:  s = sigmoid(mask[q,p]),  v = score[q] * s (one fp32 multiply);  best = the first q that
+ * attains the largest v;  solid_q = (s >= 0.5f).
+ *   counts[0][best] += 1                          the area best won             (the reference's `cur_mask_ids == k`)
+ *   counts[1][q]    += solid_q  for every kept q  q's own >= 0.5 area           (`cur_masks[k] >= 0.5`)
+ *   counts[2][best] += solid_best                 their intersection            (`mask_area` of the pixels that are written)
+ *   winner[p]        = solid_best ? best : 0xFF
+ * winner [HW] uint8 is written everywhere; counts [3,Q] int32 is ADDED into with integer atomics (bitwise reproducible; the caller zeroes it) and
+ * rows of queries that are not kept are left alone.  mask may be only 4-byte aligned and winner not at all: 16-byte loads are issued on 16-byte
+ * aligned addresses only.  1 <= Q <= 255 (0xFF is the "nobody" byte), 1 <= HW < 2^31; anything else returns hipErrorInvalidValue without a launch.
+ * With no kept query every winner is 0xFF and counts stays as it is.  Non-finite logits: a NaN product never wins (v > best is false), a pixel
+ * whose kept products are all NaN has no winner (0xFF, no counter moves); score is expected finite and >= 0. */
+int rba_panoptic_merge_f32(const float* mask, const float* score, const uint8_t* keep, uint8_t* winner, int32_t* counts, int Q, int64_t HW,
+                           void* stream);
+
+/* K16a fused with the x4 bilinear upsample (align_corners=False, ATen's tap order) in front and the crop behind it, rba_reduce_up4_f32's contract:
+ * mask_lowres [Q,h,w]; the per-pixel rule above runs on rows < crop_h and columns < crop_w of the virtual [Q,4h,4w] map; winner [crop_h,crop_w].
+ * 1 <= crop_h <= 4h, 1 <= crop_w <= 4w. */
+int rba_panoptic_merge_up4_f32(const float* mask_lowres, const float* score, const uint8_t* keep, uint8_t* winner, int32_t* counts, int Q,
+                               int h, int w, int crop_h, int crop_w, void* stream);
+
+/* K16b.  panoptic[p] = winner[p] == 0xFF ? 0 : seg_of_query[winner[p]]  (a byte >= Q counts as 0xFF).  seg_of_query [Q] int32: the segment id the
+ * host loop gave each query, 0 = dropped.  The reference's sequential `panoptic_seg[mask] = id` writes touch disjoint pixels: their order is free. */
+int rba_panoptic_assign_i32(const uint8_t* winner, const int32_t* seg_of_query, int32_t* panoptic, int Q, int64_t HW, void* stream);
+
+/* K16c.  The segment-pair histogram of panoptic evaluation (evaluation.py:152-159: np.unique(pan_gt * OFFSET + pan_pred, return_counts=True)) on
+ * dense ids: per pixel, 0 <= gt < G and 0 <= pred < P  ->  counts[gt * P + pred] += 1, otherwise bad[0] += 1.  counts [G,P] and bad [1] are int64
+ * and ADDED into with 64-bit integer atomics (the caller zeroes them); nothing is allocated or read back.  gt and pred may be only 4-byte aligned.
+ * 1 <= G, P, G * P <= 2^24, 1 <= n <= 2^40. */
+int rba_segment_pairs_accum(const int32_t* gt, const int32_t* pred, int64_t n, int G, int P, int64_t* counts, int64_t* bad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,10 @@ SIGNATURES = {
     "rba_tta_merge_f32": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "rba_resize_u8_pil_bilinear": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp],
     "rba_confusion_accum": [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp],
+    "rba_panoptic_merge_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp],
+    "rba_panoptic_merge_up4_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "rba_panoptic_assign_i32": [_vp, _vp, _vp, _i, _i64, _vp],
+    "rba_segment_pairs_accum": [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp],
     "rba_train_view_u8": [_vp, _vp],
     "rba_grad_sqnorm_f32": [_vp, _i64, ctypes.c_float, _vp, _i, _vp],
     "rba_clip_adamw_step_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, panoptic_ops
 from .h2d import to_device
 from .arch import backbone_name as _backbone_name, complete
 from .graph_replay import GraphKey, GraphReplay, capture
@@ -192,47 +192,39 @@ class MaskFormer(nn.Module):
     # ------------------------------------------------------------------ open-set panoptic inference (:394-486)
     @torch.no_grad()
     def panoptic_inference(self, mask_cls, mask_pred, open_panoptic=False, ood_threshold=-0.1, pixel_min=300,
-                           return_ood_pred=False):
+                           return_ood_pred=False, ood_mask=None):
         """mask_cls [Q,K+1] logits, mask_pred [Q,H,W] logits at the output resolution ->
         (panoptic_seg int32 [H,W], segments_info[, rba map]).  Closed-set part: the Mask2Former merge (:395-452) -- queries whose
         best class is not void and scores above ``object_mask_threshold`` compete per pixel by score x sigmoid(mask); a query
         keeps its pixels if enough of its own >= 0.5 area wins (``overlap_threshold``); "stuff" classes merge into one segment.
+        One pass over the mask planes (K16a), one read-back of its 3 Q counters, the reference's loop on the host over Python ints, one
+        gather (K16b): docs/kernels/K16.md.
         Open-set part (:454-481): the RbA map (K1) thresholded, 3x3 opened and closed, 4-connected components of at least
-        ``pixel_min`` still-unclaimed pixels become new "thing" segments of category 255."""
-        Q, H, W = mask_pred.shape
+        ``pixel_min`` still-unclaimed pixels become new "thing" segments of category 255.  ``ood_mask``: the RbA map [H,W] where the
+        caller has it already (forward() does); None: K1 runs here."""
+        return self._panoptic(mask_cls, mask_pred, None, open_panoptic, ood_threshold, pixel_min, return_ood_pred, ood_mask)
+
+    def _panoptic(self, mask_cls, mask_pred, crop, open_panoptic, ood_threshold, pixel_min, return_ood_pred, ood_mask):
+        """panoptic_inference; with ``crop`` = (H, W), mask_pred is the quarter-resolution [Q,h,w] and the merge runs on the [H,W] window of
+        its virtual x4 up-sampling (K16a's up4 form): the full-resolution planes are never written."""
+        H, W = (mask_pred.shape[-2:] if crop is None else crop)
         K = mask_cls.shape[-1] - 1
         prob_all = F.softmax(mask_cls, dim=-1)
         scores, labels = prob_all.max(-1)
         keep = labels.ne(K) & (scores > self.object_mask_threshold)
-        panoptic_seg = torch.zeros((H, W), dtype=torch.int32, device=mask_pred.device)
-        segments_info = []
-        if not bool(keep.any()):
-            return panoptic_seg, segments_info                        # (the reference also skips the open-set part here, :414-416)
-        cur_scores, cur_classes = scores[keep], labels[keep]
-        cur_masks = mask_pred[keep].sigmoid()
-        cur_mask_ids = (cur_scores.view(-1, 1, 1) * cur_masks).argmax(0)
-        current = 0
-        stuff_ids = {}
-        for k in range(cur_classes.shape[0]):
-            cls = int(cur_classes[k])
-            won = cur_mask_ids == k
-            solid = cur_masks[k] >= 0.5
-            mask = won & solid
-            mask_area, original_area, inter = int(won.sum()), int(solid.sum()), int(mask.sum())
-            if mask_area == 0 or original_area == 0 or inter == 0 or mask_area / original_area < self.overlap_threshold:
-                continue
-            isthing = cls in self.thing_classes
-            if not isthing:
-                if cls in stuff_ids:
-                    panoptic_seg[mask] = stuff_ids[cls]
-                    continue
-                stuff_ids[cls] = current + 1
-            current += 1
-            panoptic_seg[mask] = current
-            segments_info.append({"id": current, "isthing": bool(isthing), "category_id": cls})
+        classes = torch.where(keep, labels, torch.full_like(labels, -1)).tolist()     # one read-back: who is kept, and as which class
+        if all(c < 0 for c in classes):
+            # (the reference also skips the open-set part here, :414-416)
+            return torch.zeros((H, W), dtype=torch.int32, device=mask_pred.device), []
+        panoptic_seg, segments_info, current = panoptic_ops.panoptic_segments(
+            mask_pred.contiguous(), scores.contiguous(), keep.to(torch.uint8), classes, self.thing_classes, self.overlap_threshold, crop)
         if not open_panoptic:
             return panoptic_seg, segments_info
-        ood_mask = ops.rba_reduce(mask_pred.contiguous(), prob_all[:, :-1].contiguous())[0]      # -sum_k tanh(sem_k), K1
+        if ood_mask is None:
+            full = mask_pred if crop is None else ops.resample_bilinear(mask_pred.contiguous(), (4 * mask_pred.shape[-2], 4 * mask_pred.shape[-1]))[:, :H, :W]
+            ood_mask = ops.rba_reduce(full.contiguous(), prob_all[:, :-1].contiguous())[0]      # -sum_k tanh(sem_k), K1
+        elif tuple(ood_mask.shape) != (H, W):
+            raise ops.RbaHipError(f"ood_mask must have the output resolution {(H, W)}, got {tuple(ood_mask.shape)}")
         comp, n = ops.ood_components(ood_mask, ood_threshold)
         if n:
             free = panoptic_seg == 0
@@ -281,11 +273,19 @@ class MaskFormer(nn.Module):
             if return_argmax:
                 r["argmax"] = arg
             if self.panoptic_on:                                   # :337-341; masks first brought to the output resolution (:318-321)
-                mp = ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
-                if (height, width) != sizes[i]:
+                if (height, width) == sizes[i]:
+                    # the merge's resolution is `rba`'s: the RbA map is handed over, and where the padded size is exactly x4 the merge
+                    # up-samples on the fly (K16a's up4 form) instead of reading [Q,H,W] planes written for it
+                    up4 = mask_pred.shape[-2] * 4 == padded[0] and mask_pred.shape[-1] * 4 == padded[1]
+                    mp = mask_pred[i] if up4 else ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
+                    r["panoptic_seg"] = self._panoptic(mask_cls[i], mp, sizes[i] if up4 else None, self.open_panoptic, panoptic_ood_threshold,
+                                                       panoptic_pixel_min, return_panoptic_ood, rba)
+                else:
+                    mp = ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
                     mp = ops.resample_bilinear(mp, (height, width))
-                r["panoptic_seg"] = self.panoptic_inference(mask_cls[i], mp, self.open_panoptic, panoptic_ood_threshold,
-                                                            panoptic_pixel_min, return_panoptic_ood)
+                    # `rba` is the score of these resized mask logits only on the postprocess-before-inference path (on the other it comes from resized class maps)
+                    r["panoptic_seg"] = self.panoptic_inference(mask_cls[i], mp, self.open_panoptic, panoptic_ood_threshold, panoptic_pixel_min,
+                                                                return_panoptic_ood, ood_mask=rba if self.sem_seg_postprocess_before_inference else None)
             results.append(r)
         if return_ood_pred:
             return results, ood_pred                            # :350-351
