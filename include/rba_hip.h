@@ -70,6 +70,8 @@
  *   rba_panoptic_merge_f32 / rba_panoptic_merge_up4_f32 / rba_panoptic_assign_i32 <- the closed-set merge of MaskFormer.panoptic_inference
  *                                  (maskformer_model.py:395-452: sigmoid, score product, argmax, the per-query area tests' sums, the id writes)
  *   rba_segment_pairs_accum     <- pq_compute_single_core's np.unique(pan_gt * OFFSET + pan_pred) (mask2former/evaluation/evaluation.py:152-159)
+ *   rba_instance_stats_f32 / rba_instance_stats_up4_f32 / rba_instance_masks_{f32,u8} / rba_instance_masks_up4_{f32,u8} <- MaskFormer.instance_inference
+ *                                  (maskformer_model.py:503-524: the gathered planes, `> 0`, sigmoid, product, the two sums; BitMasks boxes of :520)
  *   rba_add_layer_norm_f32      <- `x = x + proj(...)` followed by nn.LayerNorm (swin.py:284-293 and the post-norm layers
  *                                  of msdeformattn.py:134-138, mask2former_transformer_decoder.py:48-58,106-118,171-175)
  *   rba_group_norm_f32          <- GroupNorm(32) [+ ReLU] behind Detectron2's Conv2d(norm=get_norm("GN"), activation)
@@ -847,6 +849,38 @@ int rba_panoptic_assign_i32(const uint8_t* winner, const int32_t* seg_of_query, 
  * and ADDED into with 64-bit integer atomics (the caller zeroes them); nothing is allocated or read back.  gt and pred may be only 4-byte aligned.
  * 1 <= G, P, G * P <= 2^24, 1 <= n <= 2^40. */
 int rba_segment_pairs_accum(const int32_t* gt, const int32_t* pred, int64_t n, int G, int P, int64_t* counts, int64_t* bad, void* stream);
+
+/* K17a.  The per-query sums of MaskFormer.instance_inference (maskformer_model.py:517-524) and the boxes it leaves commented out (:520), for every kept
+ * query in one pass over the kept planes.  mask [Q,H,W] mask logits at the output resolution; keep [Q] uint8, non-zero = the query is in the top-k.
+ * For every kept q and every pixel (x, y) with logit m > 0 (a NaN logit is not > 0 and contributes nothing):
+ *   count[q] += 1
+ *   ssum[q]  += (int64)(sigmoid(m) * 2^32)        an integer: a sigmoid of a positive logit is an fp32 value of at least ~0.5, so ssum is the EXACT
+ *                                                 sum of the fp32 sigmoids in units of 2^-32 -- independent of arrival order, bitwise reproducible
+ *   box[q]    = (min x, min y, max x, max y)      through atomic min / max
+ * count [Q] int32 and ssum [Q] int64 are ADDED into with integer atomics and box [Q,4] int32 is min / max-ed into: the caller zeroes count and ssum and
+ * sets every box to (W, H, -1, -1); rows of queries that are not kept are left alone.  mask may be only 4-byte aligned: 16-byte loads are issued on
+ * 16-byte aligned addresses only.  1 <= Q <= 255, 1 <= H * W < 2^31; anything else returns hipErrorInvalidValue without a launch. */
+int rba_instance_stats_f32(const float* mask, const uint8_t* keep, int32_t* count, int64_t* ssum, int32_t* box, int Q, int H, int W, void* stream);
+
+/* K17a fused with the x4 bilinear upsample (align_corners=False, ATen's tap order) in front and the crop behind it, rba_panoptic_merge_up4_f32's
+ * contract: mask_lowres [Q,h,w]; the rule above runs on rows < crop_h and columns < crop_w of the virtual [Q,4h,4w] map (the caller's boxes start at
+ * (crop_w, crop_h, -1, -1)).  1 <= crop_h <= 4h, 1 <= crop_w <= 4w. */
+int rba_instance_stats_up4_f32(const float* mask_lowres, const uint8_t* keep, int32_t* count, int64_t* ssum, int32_t* box, int Q, int h, int w,
+                               int crop_h, int crop_w, void* stream);
+
+/* K17b.  The result planes of instance_inference (:503, :517): out[n,p] = mask[qidx[n],p] > 0 ? 1 : 0 as float or as uint8.  mask [Q,HW], qidx [N]
+ * int32, out [N,HW].  A qidx outside [0, Q) is refused ON THE DEVICE: that plane is written as zeros and no logit is read for it.  A query may appear
+ * several times in qidx (once per class it is detected as); its plane is then read once per appearance.  out may be only element aligned: wide stores
+ * are issued on addresses aligned to four elements only.  1 <= Q, 1 <= N <= 65535, 1 <= HW < 2^31. */
+int rba_instance_masks_f32(const float* mask, const int32_t* qidx, float* out, int Q, int N, int64_t HW, void* stream);
+int rba_instance_masks_u8(const float* mask, const int32_t* qidx, uint8_t* out, int Q, int N, int64_t HW, void* stream);
+
+/* K17b on the crop_h x crop_w window of the virtual x4 map of mask_lowres [Q,h,w] (the taps of rba_instance_stats_up4_f32, so the planes agree with its
+ * counts pixel by pixel): out [N,crop_h,crop_w]. */
+int rba_instance_masks_up4_f32(const float* mask_lowres, const int32_t* qidx, float* out, int Q, int N, int h, int w, int crop_h, int crop_w,
+                               void* stream);
+int rba_instance_masks_up4_u8(const float* mask_lowres, const int32_t* qidx, uint8_t* out, int Q, int N, int h, int w, int crop_h, int crop_w,
+                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,12 @@ SIGNATURES = {
     "rba_panoptic_merge_up4_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "rba_panoptic_assign_i32": [_vp, _vp, _vp, _i, _i64, _vp],
     "rba_segment_pairs_accum": [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp],
+    "rba_instance_stats_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "rba_instance_stats_up4_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "rba_instance_masks_f32": [_vp, _vp, _vp, _i, _i, _i64, _vp],
+    "rba_instance_masks_u8": [_vp, _vp, _vp, _i, _i, _i64, _vp],
+    "rba_instance_masks_up4_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "rba_instance_masks_up4_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "rba_train_view_u8": [_vp, _vp],
     "rba_grad_sqnorm_f32": [_vp, _i64, ctypes.c_float, _vp, _i, _vp],
     "rba_clip_adamw_step_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],

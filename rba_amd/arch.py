@@ -66,6 +66,8 @@ _DEFAULTS = dict(patch_size=4, mlp_ratio=4.0, enc_points=4, enc_dim_feedforward=
                  # by panoptic / instance inference); only matters when a requested output size differs from the image size
                  postprocess_before_inference=False,
                  panoptic_on=False, open_panoptic=True, object_mask_threshold=0.0, overlap_threshold=0.0,
+                 # instance inference (maskformer_model.py:213-218, 343-346, 488-527; TEST.INSTANCE_ON, TEST.SEMANTIC_ON, TEST.DETECTIONS_PER_IMAGE)
+                 semantic_on=True, instance_on=False, test_topk_per_image=100,
                  thing_classes=[11, 12, 13, 14, 15, 16, 17, 18])   # Cityscapes train ids of the "thing" classes
 
 
@@ -122,8 +124,6 @@ def arch_from_cfg(cfg) -> dict:
     if list(M.SEM_SEG_HEAD.IN_FEATURES) != list(FEATURE_NAMES):
         unsupported.append("SEM_SEG_HEAD.IN_FEATURES != res2..res5")
     T = M.MASK_FORMER.TEST
-    if not T.SEMANTIC_ON or T.INSTANCE_ON:
-        unsupported.append("TEST.SEMANTIC_ON=False / TEST.INSTANCE_ON (only semantic and open-set panoptic inference are provided)")
     if cfg.get("SOLVER", {}).get("FORCE_REGION_PARTITION", False):
         unsupported.append("SOLVER.FORCE_REGION_PARTITION")
     if unsupported:
@@ -141,7 +141,9 @@ def arch_from_cfg(cfg) -> dict:
         dense_hybrid=bool(M.MASK_FORMER.get("DENSE_HYBRID_LOSS", False)), resnet=resnet,
         postprocess_before_inference=bool(T.get("SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE", False) or T.PANOPTIC_ON or T.INSTANCE_ON),
         panoptic_on=bool(T.PANOPTIC_ON), open_panoptic=bool(M.MASK_FORMER.get("OPEN_PANOPTIC", True)),
-        object_mask_threshold=float(T.OBJECT_MASK_THRESHOLD), overlap_threshold=float(T.OVERLAP_THRESHOLD)))
+        object_mask_threshold=float(T.OBJECT_MASK_THRESHOLD), overlap_threshold=float(T.OVERLAP_THRESHOLD),
+        semantic_on=bool(T.SEMANTIC_ON), instance_on=bool(T.INSTANCE_ON),
+        test_topk_per_image=int(cfg.get("TEST", {}).get("DETECTIONS_PER_IMAGE", 100))))
 
 
 def num_fpn_levels(a: dict) -> int:

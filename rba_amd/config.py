@@ -106,7 +106,9 @@ _DEFAULTS = {
                "CLIP_GRADIENTS": {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0},
                "AMP": {"ENABLED": False}},
     # detectron2/config/defaults.py TEST.AUG (rba_amd.test_time_augmentation); the Cityscapes base config sets [512 .. 1792], 4096, FLIP
-    "TEST": {"AUG": {"ENABLED": False, "MIN_SIZES": [400, 500, 600, 700, 800, 900, 1000, 1100, 1200], "MAX_SIZE": 4000, "FLIP": True}},
+    # ... and TEST.DETECTIONS_PER_IMAGE, the top-k of instance inference (maskformer_model.py:218)
+    "TEST": {"DETECTIONS_PER_IMAGE": 100,
+             "AUG": {"ENABLED": False, "MIN_SIZES": [400, 500, 600, 700, 800, 900, 1000, 1100, 1200], "MAX_SIZE": 4000, "FLIP": True}},
 }
 
 

@@ -384,16 +384,31 @@ class _BoxSizes:
 
 # ---------------------------------------------------------------------------------------------------------------- the mapper
 class Instances:
-    """the two fields of Detectron2's Instances the model reads"""
+    """The part of Detectron2's Instances the model uses: an image size and per-instance fields, each a tensor whose first dimension is the number of
+    instances -- ``gt_classes`` / ``gt_masks`` in training (what the model reads), ``pred_masks`` / ``pred_classes`` / ``scores`` / ``pred_boxes`` from
+    instance inference (``pred_boxes`` is a plain [N,4] tensor, XYXY).  Fields are attributes; any name may be set."""
 
-    def __init__(self, image_size, gt_classes=None, gt_masks=None):
+    def __init__(self, image_size, gt_classes=None, gt_masks=None, **fields):
         self.image_size, self.gt_classes, self.gt_masks = tuple(image_size), gt_classes, gt_masks
+        for name, value in fields.items():
+            setattr(self, name, value)
+
+    def get_fields(self):
+        """{name: value} of the fields that are set"""
+        return {k: v for k, v in vars(self).items() if k != "image_size" and v is not None}
+
+    def has(self, name):
+        return name in self.get_fields()
 
     def to(self, device):
-        return Instances(self.image_size, to_device(self.gt_classes, device), to_device(self.gt_masks, device))
+        return Instances(self.image_size, **{k: to_device(v, device) for k, v in self.get_fields().items()})
 
     def __len__(self):
-        return int(self.gt_classes.shape[0])
+        if self.gt_classes is not None:
+            return int(self.gt_classes.shape[0])
+        for v in self.get_fields().values():
+            return int(v.shape[0])
+        raise NotImplementedError("empty Instances does not support __len__")
 
 
 class MaskFormerSemanticCocoMixDatasetMapper:

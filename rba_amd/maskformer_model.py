@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, panoptic_ops
+from . import instance_ops, ops, panoptic_ops
 from .h2d import to_device
 from .arch import backbone_name as _backbone_name, complete
 from .graph_replay import GraphKey, GraphReplay, capture
@@ -69,7 +69,12 @@ class MaskFormer(nn.Module):
         self.fused_upsample = True      # K1 reads the low-res logits and up-samples on the fly (rba_reduce_up4)
         # panoptic inference (maskformer_model.py:202-220): off unless TEST.PANOPTIC_ON
         self.panoptic_on, self.open_panoptic = bool(a["panoptic_on"]), bool(a["open_panoptic"])
-        self.sem_seg_postprocess_before_inference = bool(a["postprocess_before_inference"]) or self.panoptic_on
+        # instance inference (maskformer_model.py:213-218): off unless TEST.INSTANCE_ON; TEST.SEMANTIC_ON: False drops "sem_seg" / "rba" from the results
+        self.semantic_on, self.instance_on = bool(a["semantic_on"]), bool(a["instance_on"])
+        self.test_topk_per_image = int(a["test_topk_per_image"])
+        self.instance_boxes = False                     # True: pred_boxes = the masks' bounding boxes (K17a has them anyway); False: zeros, as the reference
+        self.instance_mask_dtype = torch.float32        # pred_masks' element type: the reference's float32, or torch.uint8 (a quarter of the bytes)
+        self.sem_seg_postprocess_before_inference = bool(a["postprocess_before_inference"]) or self.panoptic_on or self.instance_on
         self.object_mask_threshold, self.overlap_threshold = float(a["object_mask_threshold"]), float(a["overlap_threshold"])
         self.thing_classes = frozenset(int(c) for c in a["thing_classes"])
         self.eval()
@@ -173,9 +178,10 @@ class MaskFormer(nn.Module):
             new_targets.append(entry)
         return new_targets
 
-    def _post(self, mask_cls, mask_pred, image_size, padded, want_sem_seg, want_argmax, score="rba"):
-        """Up-sample (:294-299), semantic inference (:381-386), crop (:330-332), RbA (evaluate_ood.py:150)."""
-        prob = _class_prob(mask_cls)
+    def _post(self, mask_cls, mask_pred, image_size, padded, want_sem_seg, want_argmax, score="rba", with_void=False):
+        """Up-sample (:294-299), semantic inference (:381-386), crop (:330-332), RbA (evaluate_ood.py:150).  with_void: semantic_inference_with_void
+        (:388-392) -- K1 on the [Q,K+1] probabilities, the void column kept."""
+        prob = F.softmax(mask_cls, dim=-1).contiguous() if with_void else _class_prob(mask_cls)
         H, W = padded
         exact4 = mask_pred.shape[-2] * 4 == H and mask_pred.shape[-1] * 4 == W
         if self.fused_upsample and exact4 and prob.shape[1] <= 32:
@@ -241,12 +247,36 @@ class MaskFormer(nn.Module):
             return panoptic_seg, segments_info, ood_mask
         return panoptic_seg, segments_info
 
+    # ------------------------------------------------------------------ instance inference (:488-527)
+    @torch.no_grad()
+    def instance_inference(self, mask_cls, mask_pred):
+        """mask_cls [Q,K+1] logits, mask_pred [Q,H,W] logits at the output resolution -> Instances(image_size) with pred_masks [N,H,W]
+        (``instance_mask_dtype``: mask_pred > 0), pred_classes [N], scores [N] (class score x mean sigmoid over the mask) and pred_boxes [N,4] (zeros as the
+        reference, or with ``instance_boxes`` the masks' XYXY boxes) of the ``test_topk_per_image`` best (query, class) pairs, in DESCENDING class score
+        (the reference's ``sorted=False`` leaves the order unspecified); with ``panoptic_on`` only the "thing" classes are kept (:506-513).  One pass over
+        the planes of the queries in the top-k (K17a) and one write of the result planes (K17b): docs/kernels/K17.md."""
+        return self._instances(mask_cls, mask_pred.contiguous(), None)
+
+    def _instances(self, mask_cls, mask, crop):
+        """instance_inference; with ``crop`` = (H, W), mask is the quarter-resolution [Q,h,w] and everything runs on the [H,W] window of its virtual x4
+        up-sampling (K17's up4 forms): the full-resolution planes are never written."""
+        from .dataset_mappers import Instances
+        planes, classes, scores, boxes = instance_ops.instance_segments(
+            mask_cls.contiguous(), mask, self.test_topk_per_image, mask_cls.shape[-1] - 1, crop, self.thing_classes if self.panoptic_on else None,
+            self.instance_boxes, self.instance_mask_dtype)
+        size = tuple(int(v) for v in (mask.shape[-2:] if crop is None else crop))
+        return Instances(size, pred_masks=planes, pred_boxes=boxes, scores=scores, pred_classes=classes)
+
     @torch.no_grad()
     def forward(self, batched_inputs, include_void=False, return_separately=False, return_aux=False,
                 return_ood_pred=False, return_argmax=False, panoptic_ood_threshold=-0.3, panoptic_pixel_min=200,
                 return_panoptic_ood=False, **kwargs):
-        if include_void or return_separately or return_aux or kwargs:
-            raise NotImplementedError("only the semantic and (open-set) panoptic inference paths of MaskFormer.forward are provided")
+        """include_void: "sem_seg" is semantic_inference_with_void's (:388-392), K + 1 channels with the void class last; "rba" stays the score over the K
+        real classes.  return_separately: -> (results, mask_cls_result, mask_pred_result) of the LAST image (:353-354), its mask logits materialised at the
+        resolution its inference heads saw."""
+        if return_aux or kwargs:
+            raise NotImplementedError("return_aux and other keyword arguments of the reference's MaskFormer.forward are not provided (semantic, panoptic "
+                                      "and instance inference are)")
         outputs, sizes, padded = self._predict_outputs(batched_inputs)
         mask_cls, mask_pred = outputs["pred_logits"], outputs["pred_masks"]
         ood_pred = None
@@ -254,41 +284,58 @@ class MaskFormer(nn.Module):
             if "ood_pred" not in outputs:
                 raise KeyError("ood_pred: the model has no DenseHybrid head (MODEL.MASK_FORMER.DENSE_HYBRID_LOSS)")
             ood_pred = ops.resample_bilinear_ac(outputs["ood_pred"].contiguous(), sizes[0])
+        up4 = mask_pred.shape[-2] * 4 == padded[0] and mask_pred.shape[-1] * 4 == padded[1]
         results = []
         for i, inp in enumerate(batched_inputs):
             height, width = inp.get("height", sizes[i][0]), inp.get("width", sizes[i][1])
-            if (height, width) != sizes[i] and self.sem_seg_postprocess_before_inference:
-                # :316-320: crop + resize the MASK LOGITS to the requested resolution first, semantic inference on those
-                up = ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
-                up = ops.resample_bilinear(up, (height, width))
-                prob = _class_prob(mask_cls[i])
-                rba, sem, arg = ops.rba_reduce(up, prob, True, return_argmax)
-            else:
-                rba, sem, arg = self._post(mask_cls[i], mask_pred[i], sizes[i], padded, True, return_argmax)
-                if (height, width) != sizes[i]:   # :330-332: sem_seg_postprocess of the class maps to the requested resolution
+            resized = (height, width) != sizes[i]
+            planes = []
+
+            def materialised():
+                """the mask logits at the output resolution (:294-299, :316-320), written once for whichever head asks"""
+                if not planes:
+                    mp = ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
+                    planes.append(ops.resample_bilinear(mp, (height, width)) if resized else mp)
+                return planes[0]
+
+            def semantic(with_void):
+                if resized and self.sem_seg_postprocess_before_inference:
+                    # :316-320: crop + resize the MASK LOGITS to the requested resolution first, semantic inference on those
+                    prob = F.softmax(mask_cls[i], dim=-1).contiguous() if with_void else _class_prob(mask_cls[i])
+                    return ops.rba_reduce(materialised(), prob, True, return_argmax and not with_void)
+                rba, sem, arg = self._post(mask_cls[i], mask_pred[i], sizes[i], padded, True, return_argmax and not with_void, with_void=with_void)
+                if resized:                       # :330-332: sem_seg_postprocess of the class maps to the requested resolution
                     sem = ops.resample_bilinear(sem, (height, width))
                     rba = -sem.tanh().sum(dim=0)
                     arg = sem.argmax(0).to(torch.int32) if return_argmax else None
-            r = {"sem_seg": sem, "rba": rba}
-            if return_argmax:
-                r["argmax"] = arg
+                return rba, sem, arg
+
+            r, rba = {}, None
+            if self.semantic_on:
+                rba, sem, arg = semantic(False)
+                r = {"sem_seg": semantic(True)[1] if include_void else sem, "rba": rba}
+                if return_argmax:
+                    r["argmax"] = arg
             if self.panoptic_on:                                   # :337-341; masks first brought to the output resolution (:318-321)
-                if (height, width) == sizes[i]:
+                if not resized:
                     # the merge's resolution is `rba`'s: the RbA map is handed over, and where the padded size is exactly x4 the merge
                     # up-samples on the fly (K16a's up4 form) instead of reading [Q,H,W] planes written for it
-                    up4 = mask_pred.shape[-2] * 4 == padded[0] and mask_pred.shape[-1] * 4 == padded[1]
-                    mp = mask_pred[i] if up4 else ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
-                    r["panoptic_seg"] = self._panoptic(mask_cls[i], mp, sizes[i] if up4 else None, self.open_panoptic, panoptic_ood_threshold,
-                                                       panoptic_pixel_min, return_panoptic_ood, rba)
+                    r["panoptic_seg"] = self._panoptic(mask_cls[i], mask_pred[i] if up4 else materialised(), sizes[i] if up4 else None, self.open_panoptic,
+                                                       panoptic_ood_threshold, panoptic_pixel_min, return_panoptic_ood, rba)
                 else:
-                    mp = ops.resample_bilinear(mask_pred[i].contiguous(), padded)[:, : sizes[i][0], : sizes[i][1]].contiguous()
-                    mp = ops.resample_bilinear(mp, (height, width))
                     # `rba` is the score of these resized mask logits only on the postprocess-before-inference path (on the other it comes from resized class maps)
-                    r["panoptic_seg"] = self.panoptic_inference(mask_cls[i], mp, self.open_panoptic, panoptic_ood_threshold, panoptic_pixel_min,
+                    r["panoptic_seg"] = self.panoptic_inference(mask_cls[i], materialised(), self.open_panoptic, panoptic_ood_threshold, panoptic_pixel_min,
                                                                 return_panoptic_ood, ood_mask=rba if self.sem_seg_postprocess_before_inference else None)
+            if self.instance_on:                                   # :343-346; the same resolution rule, K17's up4 forms where they apply
+                if not resized and up4:
+                    r["instances"] = self._instances(mask_cls[i], mask_pred[i].contiguous(), sizes[i])
+                else:
+                    r["instances"] = self._instances(mask_cls[i], materialised(), None)
             results.append(r)
         if return_ood_pred:
             return results, ood_pred                            # :350-351
+        if return_separately:
+            return results, mask_cls[-1], materialised()        # :353-354: the loop's last image
         return results
 
     # ------------------------------------------------------------------ hipGraph replay of the scoring path
