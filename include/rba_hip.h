@@ -72,6 +72,8 @@
  *   rba_segment_pairs_accum     <- pq_compute_single_core's np.unique(pan_gt * OFFSET + pan_pred) (mask2former/evaluation/evaluation.py:152-159)
  *   rba_instance_stats_f32 / rba_instance_stats_up4_f32 / rba_instance_masks_{f32,u8} / rba_instance_masks_up4_{f32,u8} <- MaskFormer.instance_inference
  *                                  (maskformer_model.py:503-524: the gathered planes, `> 0`, sigmoid, product, the two sums; BitMasks boxes of :520)
+ *   rba_subset_curves_{totals,walk,finish} / rba_labelled_tags_i32 <- OODEvaluator.evaluate_ood_bootstrapped behind ONE scoring pass: the per-trial
+ *                                  roc_curve, auc, average_precision_score and FPR95 of every image subset (support.py:247-285, 305-351)
  *   rba_add_layer_norm_f32      <- `x = x + proj(...)` followed by nn.LayerNorm (swin.py:284-293 and the post-norm layers
  *                                  of msdeformattn.py:134-138, mask2former_transformer_decoder.py:48-58,106-118,171-175)
  *   rba_group_norm_f32          <- GroupNorm(32) [+ ReLU] behind Detectron2's Conv2d(norm=get_norm("GN"), activation)
@@ -881,6 +883,43 @@ int rba_instance_masks_up4_f32(const float* mask_lowres, const int32_t* qidx, fl
                                void* stream);
 int rba_instance_masks_up4_u8(const float* mask_lowres, const int32_t* qidx, uint8_t* out, int Q, int N, int h, int w, int crop_h, int crop_w,
                               void* stream);
+
+/* K18.  The ROC and precision-recall curves of up to 64 image subsets ("trials" of a bootstrap) from ONE globally sorted pixel list
+ * (support.py:305-351 behind its scoring loop; docs/kernels/K18.md).  score [n] fp32 sorted DESCENDING; tag [n] int32 = (image_index << 1) | label, label
+ * in {0, 1}, in the same order; member [n_images] uint64, bit t set = the image belongs to trial t (bits >= T are ignored).  A threshold is a run of
+ * equal scores of the global order; a trial's curve has a point at the end of every run that holds at least one of its pixels.
+ *
+ * The list is cut into ceil(n / chunk) chunks of `chunk` pixels, one wave each; a run may span any number of chunks.  The per-chunk integers are
+ * laid out [T][2][chunks]: the (tp, cnt) planes of each trial (cnt = tp + fp) with the chunk index innermost, the dimension their prefix runs along.
+ *   rba_subset_curves_totals : per chunk c and trial t  totals[t][.][c] = (tp, cnt) of the chunk's member pixels,
+ *                              upto_end[t][.][c] = the same counted up to the LAST run end inside the chunk, has_end[c] = 1 if there is one, else 0
+ *                              (then upto_end[.][.][c] = 0).  All int32, written (not added).
+ *   rba_subset_curves_walk   : base [T][2][chunks] int64 = the counts in front of each chunk (the exclusive prefix of totals), prev [T][2][chunks]
+ *                              int64 = the counts at the last run end in front of it (0 if none).  Adds, per trial, over the run ends inside the chunk
+ *                              with a step (dtp, dfp) != (0, 0):   auroc2[t] += dfp * (tp_prev + tp)   exact, 64-bit integer atomics (the caller zeroes)
+ *                                                                  ap_part[t][c] = sum  dtp * tp / (tp + fp)   float64, in run order, dtp > 0 only
+ *   rba_subset_curves_finish : one workgroup per trial.  ap[t] = ap_part[t][0] + ap_part[t][1] + ... in chunk order (no float atomics: bitwise
+ *                              reproducible).  at95[t] = (fp, tp) int64 at the first point of the trial's ROC curve after scikit-learn's
+ *                              drop_intermediate (a point stays if the step into it differs from the step out of it, or it is the first or the last)
+ *                              whose (double)tp / (double)P > 0.95; (0, 0) when P = 0.  It walks forward from the chunk in which `ends` [T][2][chunks]
+ *                              int64 (the INCLUSIVE prefix of totals; its last column is (P, P + N)) places the crossing.
+ * 1 <= T <= 64, 1 <= n < 2^31, chunk a multiple of 64 in [64, 2^20], every image_index < n_images <= 2^30 (an index outside the table reads no
+ * membership: the pixel belongs to no trial).  Nothing is allocated, synchronised or read back. */
+int rba_subset_curves_totals(const float* score, const int32_t* tag, const uint64_t* member, int64_t n, int n_images, int T, int chunk,
+                             int32_t* totals, int32_t* upto_end, int32_t* has_end, void* stream);
+int rba_subset_curves_walk(const float* score, const int32_t* tag, const uint64_t* member, int64_t n, int n_images, int T, int chunk,
+                           const int64_t* base, const int64_t* prev, int64_t* auroc2, double* ap_part, void* stream);
+int rba_subset_curves_finish(const float* score, const int32_t* tag, const uint64_t* member, int64_t n, int n_images, int T, int chunk,
+                             const int64_t* base, const int64_t* prev, const int64_t* ends, const double* ap_part, double* ap, int64_t* at95,
+                             void* stream);
+
+/* K18's input.  Appends (score[p], (image_index << 1) | label[p]) for every pixel p of one image whose label is 0 or 1 to out_score / out_tag
+ * [capacity] at the device-side cursor: cursor[0] (int64) is advanced by the number of labelled pixels with one integer atomic per workgroup;
+ * a pixel whose slot would lie at or past `capacity` is not written and sets cursor[1] to 1.  The caller zeroes cursor once, appends any number of
+ * images and reads it once: min(cursor[0], capacity) pairs are valid when cursor[1] is 0.  Order within the buffer is unspecified (a sort follows).
+ * labels: uint8 (label_bytes = 1) or int64 (label_bytes = 8).  1 <= n < 2^31, 0 <= image_index < 2^30, capacity >= 0. */
+int rba_labelled_tags_i32(const float* score, const void* labels, int label_bytes, int64_t n, int image_index, float* out_score, int32_t* out_tag,
+                          int64_t capacity, int64_t* cursor, void* stream);
 
 #ifdef __cplusplus
 }

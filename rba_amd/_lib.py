@@ -75,6 +75,10 @@ SIGNATURES = {
     "rba_instance_masks_u8": [_vp, _vp, _vp, _i, _i, _i64, _vp],
     "rba_instance_masks_up4_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "rba_instance_masks_up4_u8": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "rba_subset_curves_totals": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "rba_subset_curves_walk": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "rba_subset_curves_finish": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rba_labelled_tags_i32": [_vp, _vp, _i, _i64, _i, _vp, _vp, _i64, _vp, _vp],
     "rba_train_view_u8": [_vp, _vp],
     "rba_grad_sqnorm_f32": [_vp, _i64, ctypes.c_float, _vp, _i, _vp],
     "rba_clip_adamw_step_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],

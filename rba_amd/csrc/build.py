@@ -8,7 +8,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "masked_xattn_bwd.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip", "pebal_loss.hip", "tta_merge.hip", "resize_u8.hip", "confusion.hip", "panoptic_merge.hip", "instance_masks.hip", "train_view.hip", "adamw_step.hip",
+SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "masked_xattn_bwd.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip", "pebal_loss.hip", "tta_merge.hip", "resize_u8.hip", "confusion.hip", "panoptic_merge.hip", "instance_masks.hip", "bootstrap_curve.hip", "train_view.hip", "adamw_step.hip",
            "swin_window_attn.hip", "swin_attn_block.hip", "group_norm.hip", "layer_norm.hip", "skinny_linear.hip", "split_linear.hip", "split_linear_dma.hip", "split_linear_gnf.hip", "gaussian_blur.hip", "open_panoptic.hip", "dense_hybrid.hip", "patch_embed.hip", "token_linear.hip", "decoder_small.hip"]
 HEADERS = ["common.h", "knobs.h", "bilinear_ac.h", "loss_reduce.h", "gaussian_blur.h", "rba_reduce_kernels.h", "split_linear_dma.h", "split_linear_h3.h", "split_linear_h3q.h", "mlp_fused_h3.h", "swin_window_attn_h3.h", "swin_attn_block.h",
            os.path.join("..", "..", "include", "rba_hip.h")]

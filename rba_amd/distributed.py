@@ -173,6 +173,21 @@ def pooled_ood_metrics(scores: torch.Tensor, labels: torch.Tensor) -> dict:
 
 
 @torch.no_grad()
+def pooled_bootstrap_metrics(scores: torch.Tensor, tags: torch.Tensor, members) -> dict:
+    """pooled_ood_metrics with the bootstrap beside it: the gather carries the int32 tags ((GLOBAL image index << 1) | label) beside the scores, and every
+    rank computes, over the same pooled pixels and the same `members` (bool [T, n_images]), {metric: {"value", "mean", "std"}} -- value = the pooled
+    metric, mean / std over the T image subsets (metrics.bootstrap_from_tags on a HIP device, the loop of ood_metrics on the CPU)."""
+    import numpy as np
+    from .metrics import bootstrap_from_tags, bootstrap_ood_metrics, ood_metrics
+
+    s = all_gather_variable(scores.reshape(-1).float().contiguous())
+    t = all_gather_variable(tags.reshape(-1).to(torch.int32).contiguous())
+    value = ood_metrics(s, t & 1)
+    boot = bootstrap_from_tags(s, t, members) if s.is_cuda else bootstrap_ood_metrics(s, t & 1, t >> 1, members)
+    return {k: {"value": value[k], "mean": float(np.mean(boot[k])), "std": float(np.std(boot[k]))} for k in value}
+
+
+@torch.no_grad()
 def pooled_confusion_flat(conf: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
     """The closed-set evaluator's state summed over every rank, as it travels: conf int64 [(K+1), (K+1)] and bad int64 [2] flattened into ONE int64
     tensor [(K+1)^2 + 2] and all_reduce(SUM)'d.  Every rank returns the same tensor; the inputs are left as they are.  Integer sums: exact, whatever the order."""

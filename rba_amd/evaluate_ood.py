@@ -127,7 +127,22 @@ def build_parser():
                    help="test-time augmentation: score every image through SemanticSegmentorWithTTA (the views of the checkpoint config's TEST.AUG: "
                         "MIN_SIZES, MAX_SIZE, FLIP); also on when that config has TEST.AUG.ENABLED.  Runs the serial one-stream loop without "
                         "graph replay, whatever --streams / --graph say")
+    p.add_argument("--bootstrap", type=int, default=0, metavar="TRIALS",
+                   help="also report every metric's mean and std over TRIALS random image subsets (OODEvaluator.evaluate_ood_bootstrapped's draws), from the "
+                        "ONE scoring pass: results.pkl then holds {value, mean, std} per metric instead of the value alone")
+    p.add_argument("--bootstrap_ratio", type=float, default=0.5, help="share of the images in every subset")
+    p.add_argument("--bootstrap_seed", type=int, default=0, help="seed of the subsets' np.random.RandomState (every rank draws the same subsets)")
     return p
+
+
+def bootstrap_members(n_images, trials, ratio, seed):
+    """--bootstrap's subsets -> bool [trials, n_images]: np.random.choice(np.arange(n), int(n * ratio), replace=False) per trial, as
+    OODEvaluator.evaluate_ood_bootstrapped draws them, from a RandomState of its own (the same on every rank)."""
+    rng = np.random.RandomState(seed)
+    members = np.zeros((trials, n_images), dtype=bool)
+    for t in range(trials):
+        members[t, rng.choice(np.arange(n_images), int(n_images * ratio), replace=False)] = True
+    return members
 
 
 def with_tta(model, cfg, args):
@@ -221,6 +236,7 @@ def _run_evaluations(model, dataset, model_name, dataset_name, args, rank=0, wor
     from .metrics import select_labelled
     score_func = SCORE_FUNCS[args.score_func]
     n = min(len(dataset), args.upper_limit)
+    bootstrap = int(getattr(args, "bootstrap", 0) or 0)      # > 0: `labels` below holds the int32 tags (image index and label) instead of the labels
     mine = D.shard_indices(n, rank, world)
     dev = model.device
     on_gpu = dev.type == "cuda"
@@ -305,7 +321,26 @@ def _run_evaluations(model, dataset, model_name, dataset_name, args, rank=0, wor
             os.makedirs(vis, exist_ok=True)
             for p in pending:
                 np.save(os.path.join(vis, f"score_{p[4]}.npy"), p[0].reshape(p[5]).cpu().numpy())
-        ss, yy = select_labelled(torch.cat([p[0] for p in pending]), torch.cat([p[1] for p in pending]))
+        if not bootstrap:
+            ss, yy = select_labelled(torch.cat([p[0] for p in pending]), torch.cat([p[1] for p in pending]))
+        elif on_gpu:
+            # --bootstrap: (score, (global image index << 1) | label) pairs appended by K18's producer at a device cursor, read once per flush
+            from . import bootstrap_ops as B
+            capacity = sum(p[0].numel() for p in pending)
+            ss = torch.empty(capacity, dtype=torch.float32, device=dev)
+            yy = torch.empty(capacity, dtype=torch.int32, device=dev)
+            cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+            for p in pending:
+                B.labelled_tags(p[0].float().contiguous(), p[1].contiguous() if p[1].dtype == torch.uint8 else p[1].to(torch.int64).contiguous(),
+                                int(p[4]), ss, yy, cursor)
+            count, overflow = cursor.tolist()
+            if overflow:
+                raise RuntimeError(f"{dataset_name}: {count} labelled pixels do not fit a buffer of {capacity}")
+            ss, yy = ss[:count].clone(), yy[:count].clone()
+        else:
+            picked = [select_labelled(p[0], p[1]) for p in pending]
+            ss = torch.cat([s_ for s_, _ in picked])
+            yy = torch.cat([(int(p[4]) << 1) | y_.to(torch.int32) for p, (_, y_) in zip(pending, picked)])
         if on_gpu:
             for p in pending:                                      # produced on a side stream, last used here on the main stream
                 for t_ in (p[0], p[1], p[3]):
@@ -380,6 +415,9 @@ def _run_evaluations(model, dataset, model_name, dataset_name, args, rank=0, wor
         if proc_stats.get("items"):
             timing["decode_processes_ms_per_sample"] = {n: round(v / proc_stats["items"] * 1e3, 2) for n, v in proc_stats.items() if n != "items"}
     s_all = torch.cat(scores) if scores else torch.empty(0, device=dev)
+    if bootstrap:
+        t_all = torch.cat(labels) if labels else torch.empty(0, dtype=torch.int32, device=dev)
+        return D.pooled_bootstrap_metrics(s_all, t_all, bootstrap_members(n, bootstrap, args.bootstrap_ratio, args.bootstrap_seed))
     y_all = torch.cat(labels) if labels else torch.empty(0, dtype=torch.bool, device=dev)
     return D.pooled_ood_metrics(s_all, y_all)
 

@@ -89,6 +89,62 @@ def roc_at_tpr95(scores: torch.Tensor, labels: torch.Tensor):
     return float(auroc), 0, float(thr[-1])
 
 
+def _member_matrix(members):
+    """members -> bool numpy [T, n_images]: row t names the images of trial t"""
+    import numpy as np
+    m = np.asarray(members.cpu() if torch.is_tensor(members) else members).astype(bool)
+    if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f"members must be [T, n_images] with at least one trial and one image, got shape {m.shape}")
+    return m
+
+
+@torch.no_grad()
+def bootstrap_from_tags(score: torch.Tensor, tag: torch.Tensor, members) -> dict:
+    """The metrics of every trial from ONE sort of the pooled pixels on a HIP device (K18, rba_amd.bootstrap_ops).  score fp32 [n] in any order, tag int32
+    [n] = (image_index << 1) | label (what bootstrap_ops.labelled_tags appends), members bool [T, n_images].  More than 64 trials run as several calls
+    over the same sorted arrays.  One read-back, of the trials' six numbers.  -> {"auroc", "aupr", "fpr95"}: float64 numpy arrays [T]; a trial without a
+    pixel raises ValueError as ood_metrics does, one without a positive (or a negative) gets the NaNs ood_metrics gives."""
+    import numpy as np
+    from . import bootstrap_ops as B
+    m = _member_matrix(members)
+    s, order = torch.sort(score.reshape(-1), descending=True)
+    t = tag.reshape(-1)[order].contiguous()
+    del order
+    parts = []
+    for t0 in range(0, m.shape[0], B.MAX_TRIALS):
+        rows = m[t0:t0 + B.MAX_TRIALS]
+        r = B.subset_curves(s, t, B.member_words(rows, s.device), int(rows.shape[0]))
+        parts.append(torch.stack([r["P"].double(), r["N"].double(), r["auroc2"].double(), r["ap"], r["fp95"].double(), r["tp95"].double()]))
+    P, N, auroc2, ap, fp95, _ = torch.cat(parts, 1).cpu().numpy()                  # (the integers are below 2^53 except auroc2, which is rounded once)
+    if bool(np.any(P + N == 0)):
+        raise ValueError("no labelled pixels")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return {"auroc": auroc2 / (2.0 * P * N), "aupr": ap / P, "fpr95": fp95 / N}
+
+
+@torch.no_grad()
+def bootstrap_ood_metrics(scores: torch.Tensor, labels: torch.Tensor, image_ids: torch.Tensor, members) -> dict:
+    """ood_metrics of T image subsets of one pooled pixel set (OODEvaluator.evaluate_ood_bootstrapped behind its scoring loop, support.py:305-351).
+    scores [n] float, labels [n] in {0, 1}, image_ids [n] (the image each pixel came from), members bool [T, n_images]: trial t is the pixels whose image i
+    has members[t, i].  -> {"auroc", "aupr", "fpr95"}: float64 numpy arrays [T].
+    On a HIP device: one sort and K18 (bootstrap_from_tags).  On the CPU: the loop of ood_metrics over the subsets -- the definition, and the tests' truth."""
+    import numpy as np
+    m = _member_matrix(members)
+    scores, labels, image_ids = scores.reshape(-1), labels.reshape(-1), image_ids.reshape(-1)
+    if not (scores.numel() == labels.numel() == image_ids.numel()):
+        raise ValueError("scores, labels and image_ids differ in size")
+    if scores.is_cuda:
+        tag = ((image_ids.to(torch.int64) << 1) | (labels != 0).to(torch.int64)).to(torch.int32)
+        return bootstrap_from_tags(scores.float(), tag, m)
+    out = {"auroc": [], "aupr": [], "fpr95": []}
+    ids = image_ids.to(torch.int64)
+    for row in m:
+        sel = torch.from_numpy(row)[ids]
+        for k, v in ood_metrics(scores[sel], labels[sel]).items():
+            out[k].append(v)
+    return {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+
+
 @torch.no_grad()
 def select_labelled(anomaly_score: torch.Tensor, ood_gts: torch.Tensor):
     """Keep pixels labelled 0 (inlier) or 1 (OoD); everything else (255) is ignored (support.py:275-285)."""

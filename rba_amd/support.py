@@ -179,12 +179,17 @@ class OODEvaluator:
             return anomaly_score, ood_gts, np.array(predictions)
         return anomaly_score, ood_gts
 
-    def evaluate_ood_bootstrapped(self, dataset, ratio, trials, device=torch.device("cpu"), batch_size=1, num_workers=10):
+    def evaluate_ood_bootstrapped(self, dataset, ratio, trials, device=torch.device("cpu"), batch_size=1, num_workers=10, one_pass=False):
         """Metrics over `trials` random subsets of ratio * len(dataset) images -> (means, stds) in percent
-        (support.py:305-351; np.random.choice without replacement, as there)."""
+        (support.py:305-351; np.random.choice without replacement, as there).
+        one_pass=True: every image is scored ONCE and the trials are subsets of that one pooled pixel set (metrics.bootstrap_ood_metrics; on a HIP device
+        one sort and K18) -- the same np.random.choice calls in the same order, so the same subsets and, to round-off, the same (means, stds)."""
         from torch.utils.data import DataLoader, Subset
         results = {}
         n = len(dataset)
+        if one_pass:
+            return self._bootstrapped_one_pass(dataset, [np.random.choice(np.arange(n), int(n * ratio), replace=False) for _ in range(trials)],
+                                               device, batch_size, num_workers)
         for _ in range(trials):
             idx = np.random.choice(np.arange(n), int(n * ratio), replace=False)
             loader = DataLoader(Subset(dataset, idx.tolist()), batch_size=batch_size, num_workers=num_workers)
@@ -193,4 +198,39 @@ class OODEvaluator:
                 results.setdefault(k, []).append(v)
         means = {k: float(np.mean(v)) * 100.0 for k, v in results.items()}
         stds = {k: float(np.std(v)) * 100.0 for k, v in results.items()}
+        return means, stds
+
+    def _bootstrapped_one_pass(self, dataset, draws, device, batch_size, num_workers):
+        """evaluate_ood_bootstrapped(one_pass=True) behind its draws.  A trial of the re-scoring loop is cut at compute_anomaly_scores' `upper_limit`
+        images of its draw; the membership rows are cut the same way."""
+        import inspect
+        from torch.utils.data import DataLoader
+        from .metrics import bootstrap_from_tags, bootstrap_ood_metrics
+        n = len(dataset)
+        limit = inspect.signature(self.compute_anomaly_scores).parameters["upper_limit"].default
+        members = np.zeros((len(draws), n), dtype=bool)
+        for t, idx in enumerate(draws):
+            members[t, idx[:limit]] = True
+        loader = DataLoader(dataset, batch_size=batch_size, num_workers=num_workers)
+        score, gts = self.compute_anomaly_scores(loader=loader, device=device, return_preds=False, upper_limit=n)
+        dev = getattr(self.model, "device", torch.device("cpu")) if self.model is not None else torch.device("cpu")
+        maps = [(torch.as_tensor(np.asarray(score[i])).to(dev).squeeze(), torch.as_tensor(np.asarray(gts[i])).to(dev).squeeze()) for i in range(n)]
+        if dev.type == "cuda":
+            from . import bootstrap_ops as B
+            capacity = sum(s.numel() for s, _ in maps)
+            out_s = torch.empty(capacity, dtype=torch.float32, device=dev)
+            out_t = torch.empty(capacity, dtype=torch.int32, device=dev)
+            cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+            for i, (s, g) in enumerate(maps):
+                B.labelled_tags(s.float().contiguous(), g.contiguous() if g.dtype == torch.uint8 else g.to(torch.int64).contiguous(), i, out_s, out_t, cursor)
+            count, overflow = cursor.tolist()                                   # the one read-back in front of the sort
+            if overflow:
+                raise RuntimeError(f"labelled_tags: {count} labelled pixels do not fit a buffer of {capacity}")
+            r = bootstrap_from_tags(out_s[:count], out_t[:count], members)
+        else:
+            picked = [select_labelled(s, g) for s, g in maps]
+            ids = torch.cat([torch.full((s.numel(),), i, dtype=torch.int64) for i, (s, _) in enumerate(picked)])
+            r = bootstrap_ood_metrics(torch.cat([s for s, _ in picked]), torch.cat([y for _, y in picked]), ids, members)
+        means = {k: float(np.mean(v)) * 100.0 for k, v in r.items()}
+        stds = {k: float(np.std(v)) * 100.0 for k, v in r.items()}
         return means, stds
