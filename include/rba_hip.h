@@ -921,6 +921,26 @@ int rba_subset_curves_finish(const float* score, const int32_t* tag, const uint6
 int rba_labelled_tags_i32(const float* score, const void* labels, int label_bytes, int64_t n, int image_index, float* out_score, int32_t* out_tag,
                           int64_t capacity, int64_t* cursor, void* stream);
 
+/* K19 -- the MiT (SegFormer) backbone's pieces that are not Linears or LayerNorms (mask2former/modeling/backbone/mix_transformer.py;
+ * docs/kernels/K19.md).  No atomics, no workspace, nothing allocated, synchronised or read back; every output has one fixed summation order.
+ *
+ * K19a.  The spatial-reduction attention core (:113-117): out[b,n,h,:] = softmax_s(q[b,n,h,:] . k[b,s,h,:] * scale) v[b,s,h,:].  q [B,N,nH*hd] (unscaled),
+ * kv [B,S,2*nH*hd] as the kv Linear leaves it (k = the first nH*hd columns, v = the rest, head-major), out [B,N,nH*hd] head-major.  Flash-style, online
+ * softmax in fp32, exact fp32 products (v_mfma_f32_32x32x2_f32): nothing of size [B*nH,N,S] exists.  hd in {32, 64}, N >= 1, 1 <= S <= 2^30, B and nH
+ * <= 65535, pointers 16-byte aligned; anything else returns hipErrorInvalidValue without a launch. */
+int rba_sr_attn_f32(const float* q, const float* kv, float* out, int B, int N, int S, int nH, int hd, float scale, void* stream);
+
+/* K19b.  y = GELU(depthwise3x3(x) + bias) (erf GELU, stride 1, zero padding 1; Mlp :53-55, DWConv :384-390) on channels-last tokens x, y [B,H*W,C].
+ * w9 [9,C] is the [C,1,3,3] weight tap-major (w9[3 ky + kx][c]).  C % 4 == 0, pointers 16-byte aligned.  Images are independent: no row of image
+ * b + 1 feeds the padding of image b. */
+int rba_dwconv3x3_gelu_nhwc_f32(const float* x, const float* w9, const float* bias, float* y, int B, int H, int W, int C, void* stream);
+
+/* K19c.  The operand of a k x k / stride / pad convolution as a GEMM: cols [B*Ho*Wo, Kp] with Ho = floor((H + 2 pad - k) / stride) + 1 (0 where no
+ * window fits; Wo alike), column (ky * k + kx) * C + c = x[b][oy * stride - pad + ky][ox * stride - pad + kx][c], zeros outside the image and in
+ * columns k*k*C .. Kp - 1.  x: channels-last [B,H,W,C], or with nchw_in != 0 the [B,C,H,W] image batch.  Kp % 4 == 0, Kp >= k*k*C, 0 <= pad < k <= 64,
+ * cols 16-byte aligned. */
+int rba_im2col_nhwc_f32(const float* x, float* cols, int B, int H, int W, int C, int k, int stride, int pad, int Kp, int nchw_in, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

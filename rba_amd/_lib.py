@@ -79,6 +79,9 @@ SIGNATURES = {
     "rba_subset_curves_walk": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "rba_subset_curves_finish": [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rba_labelled_tags_i32": [_vp, _vp, _i, _i64, _i, _vp, _vp, _i64, _vp, _vp],
+    "rba_sr_attn_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp],
+    "rba_dwconv3x3_gelu_nhwc_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "rba_im2col_nhwc_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "rba_train_view_u8": [_vp, _vp],
     "rba_grad_sqnorm_f32": [_vp, _i64, ctypes.c_float, _vp, _i, _vp],
     "rba_clip_adamw_step_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],

@@ -15,14 +15,38 @@ RESNET50 = dict(depth=50, stem_out=64, res2_out=256, width=64, stride_in_1x1=Fal
 RESNET_STAGE_BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 
 
+# MixVisionTransformer variants (mask2former/modeling/backbone/mix_transformer.py:394-493): qkv_bias, LayerNorm eps 1e-6 in the blocks and stage norms
+def _mit(embed_dims, depths):
+    return dict(embed_dims=list(embed_dims), num_heads=[1, 2, 5, 8], depths=list(depths), sr_ratios=[8, 4, 2, 1], mlp_ratio=4)
+
+
+MIT_VARIANTS = {
+    "mit_b0": _mit([32, 64, 160, 256], [2, 2, 2, 2]),
+    "mit_b1": _mit([64, 128, 320, 512], [2, 2, 2, 2]),
+    "mit_b2": _mit([64, 128, 320, 512], [3, 4, 6, 3]),
+    "mit_b3": _mit([64, 128, 320, 512], [3, 4, 18, 3]),
+    "mit_b4": _mit([64, 128, 320, 512], [3, 8, 27, 3]),
+    "mit_b5": _mit([64, 128, 320, 512], [3, 6, 40, 3]),
+}
+# the reference's MiT names its outputs stage1..stage4 (:260-272); the pixel decoder here keeps one set of names
+MIT_STAGE_NAMES = {"stage1": "res2", "stage2": "res3", "stage3": "res4", "stage4": "res5"}
+
+
 def feature_channels(a: dict) -> dict:
     """channels of res2..res5 for the arch's backbone"""
     if a.get("resnet"):
         return {f: a["resnet"]["res2_out"] * 2 ** k for k, f in enumerate(FEATURE_NAMES)}
+    if a.get("mit"):
+        return dict(zip(FEATURE_NAMES, a["mit"]["embed_dims"]))
     return {f: a["embed_dim"] * 2 ** k for k, f in enumerate(FEATURE_NAMES)}
 
 
 def backbone_name(a: dict) -> str:
+    if a.get("mit"):
+        for name, v in MIT_VARIANTS.items():
+            if v == a["mit"]:
+                return name
+        return "MixVisionTransformer"
     return "build_resnet_backbone" if a.get("resnet") else "D2SwinTransformer"
 
 # Named architectures of BASELINE.json's configs (values from ckpts/*/config.yaml and the
@@ -53,6 +77,14 @@ ARCHS = {
     "tiny1_dh": dict(embed_dim=32, depths=[2, 2, 2, 2], num_heads=[1, 2, 4, 8], window_size=6,
                      conv_dim=64, mask_dim=64, nheads=2, num_queries=16, num_classes=19,
                      dim_feedforward=128, enc_layers=2, dec_layers=1, enc_in=["res5"], dense_hybrid=True),
+    # MiT backbones (mit_b0: head_dim 32; mit_b1: head_dim 64) under tiny1's head sizes
+    "tiny1_mit_b0": dict(mit=MIT_VARIANTS["mit_b0"], conv_dim=64, mask_dim=64, nheads=2, num_queries=16, num_classes=19,
+                         dim_feedforward=128, enc_layers=2, dec_layers=1, enc_in=["res5"]),
+    "tiny1_mit_b1": dict(mit=MIT_VARIANTS["mit_b1"], conv_dim=64, mask_dim=64, nheads=2, num_queries=16, num_classes=19,
+                         dim_feedforward=128, enc_layers=2, dec_layers=1, enc_in=["res5"]),
+    # configs/cityscapes/semantic-segmentation/mix_transformer/maskformer_2_mit_b5_in21k_1dl.yaml
+    "mit_b5_1dl": dict(mit=MIT_VARIANTS["mit_b5"], conv_dim=256, mask_dim=256, nheads=8, num_queries=100, num_classes=19,
+                       dim_feedforward=2048, enc_layers=6, dec_layers=1, enc_in=["res5"]),
 }
 
 _DEFAULTS = dict(patch_size=4, mlp_ratio=4.0, enc_points=4, enc_dim_feedforward=1024,
@@ -61,6 +93,7 @@ _DEFAULTS = dict(patch_size=4, mlp_ratio=4.0, enc_points=4, enc_dim_feedforward=
                  # DenseHybrid `ood_pred` head on the mask features (MODEL.MASK_FORMER.DENSE_HYBRID_LOSS, config.py:220)
                  dense_hybrid=False,
                  resnet=None,                     # dict(depth, stem_out, res2_out, width, stride_in_1x1) for build_resnet_backbone
+                 mit=None,                        # dict(embed_dims, num_heads, depths, sr_ratios, mlp_ratio) for mit_b0..mit_b5
                  # panoptic inference (maskformer_model.py:202-220; config.py:57-59, 243)
                  # sem_seg_postprocess on the mask logits BEFORE semantic inference (maskformer_model.py:205-209: the flag, or implied
                  # by panoptic / instance inference); only matters when a requested output size differs from the image size
@@ -83,8 +116,8 @@ def arch_from_cfg(cfg) -> dict:
     M = cfg.MODEL
     if M.META_ARCHITECTURE != "MaskFormer":
         raise ValueError(f"unsupported META_ARCHITECTURE {M.META_ARCHITECTURE!r}")
-    if M.BACKBONE.NAME not in ("D2SwinTransformer", "build_resnet_backbone"):
-        raise NotImplementedError(f"backbone {M.BACKBONE.NAME!r}: D2SwinTransformer and build_resnet_backbone are provided")
+    if M.BACKBONE.NAME not in ("D2SwinTransformer", "build_resnet_backbone") + tuple(MIT_VARIANTS):
+        raise NotImplementedError(f"backbone {M.BACKBONE.NAME!r}: D2SwinTransformer, build_resnet_backbone and mit_b0..mit_b5 are provided")
     if M.SEM_SEG_HEAD.PIXEL_DECODER_NAME != "MSDeformAttnPixelDecoder":
         raise NotImplementedError(M.SEM_SEG_HEAD.PIXEL_DECODER_NAME)
     if M.MASK_FORMER.TRANSFORMER_DECODER_NAME != "MultiScaleMaskedTransformerDecoder":
@@ -93,8 +126,12 @@ def arch_from_cfg(cfg) -> dict:
         raise NotImplementedError(M.MASK_FORMER.TRANSFORMER_IN_FEATURE)
     S = M.SWIN
     unsupported = []
-    resnet = None
-    if M.BACKBONE.NAME == "build_resnet_backbone":
+    resnet = mit = None
+    feature_names = list(FEATURE_NAMES)      # what the config calls res2..res5
+    if M.BACKBONE.NAME in MIT_VARIANTS:      # the class fixes every size (mix_transformer.py:394-493): MODEL.SWIN is not read
+        mit = dict(MIT_VARIANTS[M.BACKBONE.NAME])
+        feature_names = list(MIT_STAGE_NAMES)
+    elif M.BACKBONE.NAME == "build_resnet_backbone":
         Rn = M.RESNETS
         if Rn.DEPTH not in RESNET_STAGE_BLOCKS or Rn.get("NUM_GROUPS", 1) != 1 or Rn.get("RES5_DILATION", 1) != 1:
             unsupported.append("RESNETS: only bottleneck depths 50/101/152, one group, no dilation")
@@ -121,8 +158,13 @@ def arch_from_cfg(cfg) -> dict:
         unsupported.append(f"SEM_SEG_HEAD.NORM={M.SEM_SEG_HEAD.NORM!r}")
     if M.SEM_SEG_HEAD.CONVS_DIM != M.MASK_FORMER.HIDDEN_DIM:
         unsupported.append("CONVS_DIM != HIDDEN_DIM (decoder input_proj conv)")
-    if list(M.SEM_SEG_HEAD.IN_FEATURES) != list(FEATURE_NAMES):
-        unsupported.append("SEM_SEG_HEAD.IN_FEATURES != res2..res5")
+    if list(M.SEM_SEG_HEAD.IN_FEATURES) != feature_names:
+        unsupported.append(f"SEM_SEG_HEAD.IN_FEATURES != {feature_names[0]}..{feature_names[-1]}")
+    enc_in = list(M.SEM_SEG_HEAD.DEFORMABLE_TRANSFORMER_ENCODER_IN_FEATURES)
+    if any(f not in feature_names for f in enc_in):
+        unsupported.append(f"DEFORMABLE_TRANSFORMER_ENCODER_IN_FEATURES outside {feature_names[0]}..{feature_names[-1]}")
+    else:
+        enc_in = [FEATURE_NAMES[feature_names.index(f)] for f in enc_in]
     T = M.MASK_FORMER.TEST
     if cfg.get("SOLVER", {}).get("FORCE_REGION_PARTITION", False):
         unsupported.append("SOLVER.FORCE_REGION_PARTITION")
@@ -135,10 +177,10 @@ def arch_from_cfg(cfg) -> dict:
         num_queries=M.MASK_FORMER.NUM_OBJECT_QUERIES, num_classes=M.SEM_SEG_HEAD.NUM_CLASSES,
         dim_feedforward=M.MASK_FORMER.DIM_FEEDFORWARD, enc_layers=M.SEM_SEG_HEAD.TRANSFORMER_ENC_LAYERS,
         dec_layers=M.MASK_FORMER.DEC_LAYERS - 1,
-        enc_in=list(M.SEM_SEG_HEAD.DEFORMABLE_TRANSFORMER_ENCODER_IN_FEATURES),
+        enc_in=enc_in,
         common_stride=M.SEM_SEG_HEAD.COMMON_STRIDE, size_divisibility=M.MASK_FORMER.SIZE_DIVISIBILITY,
         pixel_mean=list(M.PIXEL_MEAN), pixel_std=list(M.PIXEL_STD),
-        dense_hybrid=bool(M.MASK_FORMER.get("DENSE_HYBRID_LOSS", False)), resnet=resnet,
+        dense_hybrid=bool(M.MASK_FORMER.get("DENSE_HYBRID_LOSS", False)), resnet=resnet, mit=mit,
         postprocess_before_inference=bool(T.get("SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE", False) or T.PANOPTIC_ON or T.INSTANCE_ON),
         panoptic_on=bool(T.PANOPTIC_ON), open_panoptic=bool(M.MASK_FORMER.get("OPEN_PANOPTIC", True)),
         object_mask_threshold=float(T.OBJECT_MASK_THRESHOLD), overlap_threshold=float(T.OVERLAP_THRESHOLD),
@@ -182,6 +224,36 @@ def _swin_shapes(a, out, lin, norm):
 
 
 
+def _mit_shapes(a, out, lin, norm):
+    """mix_transformer.py:207-258: patch_embed{s}, block{s}.{i}, norm{s} for s = 1..4; attn.sr / attn.norm only where sr_ratio > 1"""
+    f32 = torch.float32
+    m = a["mit"]
+    cin = 3
+    for s, (C, depth, sr) in enumerate(zip(m["embed_dims"], m["depths"], m["sr_ratios"]), start=1):
+        k = 7 if s == 1 else 3
+        out[f"backbone.patch_embed{s}.proj.weight"] = ((C, cin, k, k), f32)
+        out[f"backbone.patch_embed{s}.proj.bias"] = ((C,), f32)
+        norm(f"backbone.patch_embed{s}.norm", C)
+        hidden = int(C * m["mlp_ratio"])
+        for b in range(depth):
+            p = f"backbone.block{s}.{b}"
+            norm(p + ".norm1", C)
+            lin(p + ".attn.q", C, C)
+            lin(p + ".attn.kv", 2 * C, C)
+            lin(p + ".attn.proj", C, C)
+            if sr > 1:
+                out[p + ".attn.sr.weight"] = ((C, C, sr, sr), f32)
+                out[p + ".attn.sr.bias"] = ((C,), f32)
+                norm(p + ".attn.norm", C)
+            norm(p + ".norm2", C)
+            lin(p + ".mlp.fc1", hidden, C)
+            out[p + ".mlp.dwconv.dwconv.weight"] = ((hidden, 1, 3, 3), f32)
+            out[p + ".mlp.dwconv.dwconv.bias"] = ((hidden,), f32)
+            lin(p + ".mlp.fc2", C, hidden)
+        norm(f"backbone.norm{s}", C)
+        cin = C
+
+
 def state_dict_shapes(arch: dict) -> dict:
     """{key: (shape, dtype)} of the reference MaskFormer state dict restricted to this path
     (everything except ``criterion.empty_weight``)."""
@@ -220,6 +292,8 @@ def state_dict_shapes(arch: dict) -> dict:
                 convbn(p + ".conv3", cout, bott, 1)
                 cin = cout
             cout, bott = cout * 2, bott * 2
+    elif a.get("mit"):
+        _mit_shapes(a, out, lin, norm)
     else:
         _swin_shapes(a, out, lin, norm)
 

@@ -22,7 +22,7 @@ def _ceil_div(a, b):
 def stages(arch, h, w):
     """-> list of (stage name, flops, bytes) for ONE image of h x w pixels."""
     a = complete(arch)
-    if a.get("resnet"):
+    if a.get("resnet") or a.get("mit"):
         raise NotImplementedError("cost model covers the Swin configurations (BASELINE configs[1..4])")
     d = a["size_divisibility"] if a["size_divisibility"] > 0 else 32
     H, W = _ceil_div(h, d) * d, _ceil_div(w, d) * d

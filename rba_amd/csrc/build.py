@@ -8,7 +8,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "masked_xattn_bwd.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip", "pebal_loss.hip", "tta_merge.hip", "resize_u8.hip", "confusion.hip", "panoptic_merge.hip", "instance_masks.hip", "bootstrap_curve.hip", "train_view.hip", "adamw_step.hip",
+SOURCES = ["rba_reduce.hip", "rba_reduce_bwd.hip", "resample.hip", "ms_deform_attn.hip", "ms_deform_attn_bwd.hip", "masked_xattn.hip", "masked_xattn_bwd.hip", "mask_logits.hip", "mask_logits_bwd.hip", "point_loss.hip", "outlier_tail.hip", "dense_hybrid_loss.hip", "pebal_loss.hip", "tta_merge.hip", "resize_u8.hip", "confusion.hip", "panoptic_merge.hip", "instance_masks.hip", "bootstrap_curve.hip", "mit_attn.hip", "mit_conv.hip", "train_view.hip", "adamw_step.hip",
            "swin_window_attn.hip", "swin_attn_block.hip", "group_norm.hip", "layer_norm.hip", "skinny_linear.hip", "split_linear.hip", "split_linear_dma.hip", "split_linear_gnf.hip", "gaussian_blur.hip", "open_panoptic.hip", "dense_hybrid.hip", "patch_embed.hip", "token_linear.hip", "decoder_small.hip"]
 HEADERS = ["common.h", "knobs.h", "bilinear_ac.h", "loss_reduce.h", "gaussian_blur.h", "rba_reduce_kernels.h", "split_linear_dma.h", "split_linear_h3.h", "split_linear_h3q.h", "mlp_fused_h3.h", "swin_window_attn_h3.h", "swin_attn_block.h",
            os.path.join("..", "..", "include", "rba_hip.h")]
@@ -29,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # the other wave -- fc1 of Swin stage 3: 65 us packed, 70 us unpacked; the whole network: equal within noise; the one-kernel stage-1 MLP: 174
 # vs 169 us (profiles/r03_k6_h3q.txt).  RBA_NO_PACKED_FP32=1 python -m rba_amd.csrc.build --force rebuilds the matrix-pipe files without it.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-MFMA_SOURCES = ({"split_linear.hip", "split_linear_dma.hip", "mask_logits.hip", "mask_logits_bwd.hip", "masked_xattn.hip", "skinny_linear.hip"}
+MFMA_SOURCES = ({"split_linear.hip", "split_linear_dma.hip", "mask_logits.hip", "mask_logits_bwd.hip", "masked_xattn.hip", "skinny_linear.hip", "mit_attn.hip"}
                 if os.environ.get("RBA_NO_PACKED_FP32") == "1" else set())
 # Always without packed fp32: the GroupNorm-folded projection (split_linear_gnf.hip says why: a packed multiply with the cross select on source 1 went wrong there).
 # ms_deform_attn_bwd.hip: atomic-bound (docs/kernels/K2.md), and the compiler packed its tap differences into the cross-select form the gate refuses (rule P).

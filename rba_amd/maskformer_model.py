@@ -16,6 +16,7 @@ from .h2d import to_device
 from .arch import backbone_name as _backbone_name, complete
 from .graph_replay import GraphKey, GraphReplay, capture
 from .lru import ShapeCache
+from .modeling.backbone import mix_transformer as _mix_transformer  # noqa: F401  (registers mit_b0..mit_b5)
 from .modeling.backbone import resnet as _resnet  # noqa: F401  (registers build_resnet_backbone)
 from .modeling.backbone import swin as _swin  # noqa: F401  (registers D2SwinTransformer)
 from .modeling.meta_arch import mask_former_head as _head  # noqa: F401
